@@ -33,6 +33,19 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 FP64_PEAK_TFLOPS = 78.6    # MI355X public FP64 vector peak (not in the local guide)
 TRAFFIC_PROFILE = "r5_cfg2/pmc_grad_kernel.json"   # PMC summary of the dominant kernel (see the roofline.traffic comment)
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(path, draws):
+    """--dump-outputs DIR: what the timed path hands its caller for its last step -- the draw of every chain in the last timed
+    iteration -- as DIR/draws.npy, float64 [chains][parameters].  Beyond DUMP_MAX_BYTES (cfg 5: 10 004 parameters x 1024 chains) a
+    fixed, seeded sample of the chains is kept, in chain order: the same chains in every run with the same arguments."""
+    draws = np.ascontiguousarray(draws, dtype=np.float64)
+    if draws.nbytes > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // draws[0].nbytes
+        draws = draws[np.sort(np.random.default_rng(0).choice(len(draws), keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "draws.npy"), draws)
 
 
 def cpu_baseline(spec, L, seconds_budget=30.0):
@@ -206,7 +219,8 @@ def live_traffic(a, kernel):
         "last %d launches of %s) over `bench.py --steps 4` of the same build" % (kb["FETCH_SIZE"], kb["WRITE_SIZE"], n_used["FETCH_SIZE"], kernel))
 
 
-def side_run(w, R, models, rank, local_rank, world, dist, steps, warmup, cpg, rows=None, sampler="default", strict=False, model=None, spec=None):
+def side_run(w, R, models, rank, local_rank, world, dist, steps, warmup, cpg, rows=None, sampler="default", strict=False, model=None, spec=None,
+             dump=None):
     """One of the other BASELINE.json configurations (the judged bench line is cfg 2), timed like the main leg: `warmup` untimed
     sampler warm-up iterations, then `steps` timed iterations + (N > 1) the one all-gather; returns the result dict on rank 0.
       cfg1 funnel 10-d, HMC L=5                                  (data-free, chain-per-wavefront engine)
@@ -280,6 +294,8 @@ def side_run(w, R, models, rank, local_rank, world, dist, steps, warmup, cpg, ro
         else:   # the first `nshow` parameters of every draw, fetched a few iterations at a time (cfg 5: 10 004 parameters per draw)
             step_it = max(1, int(2.5e8 // max(1, cpg * spec.n_params)))
             draws = np.concatenate([s.draws(f, min(step_it, steps - f))[:, :, :nshow] for f in range(0, steps, step_it)], axis=1)
+        if dump:
+            dump_outputs(dump, gathered[:, -1, :] if comm is not None else s.draws(steps - 1, 1)[:, 0, :])
     s.close()
     if own:
         model.close()
@@ -339,7 +355,7 @@ def side_workload(a, R, models, rank, local_rank, world, dist):
     w = a.workload
     cpg = a.chains_per_gpu if a.chains_per_gpu != 1024 or w not in ("cfg4",) else 256
     out = side_run(w, R, models, rank, local_rank, world, dist, a.steps, a.warmup, cpg, rows=None if a.rows == 1_000_000 else a.rows,
-                   sampler=a.sampler, strict=a.strict)
+                   sampler=a.sampler, strict=a.strict, dump=a.dump_outputs)
     if rank == 0:
         print(json.dumps(out))
 
@@ -439,7 +455,12 @@ def main():
     ap.add_argument("--grad-chains", type=int, default=0)
     ap.add_argument("--grad-unroll", type=int, default=0)
     ap.add_argument("--grad-splits", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed iteration's draw of every chain to DIR/draws.npy (float64, "
+                         "[chains][parameters], at most 64 MB: a fixed, seeded sample of the chains beyond that)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -498,6 +519,8 @@ def main():
     steps_local = sum(st.leapfrogSteps for st in stats)
     assert steps_local == K * L * cpg, (steps_local, K, L, cpg)
     total_steps = steps_local * world
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, draws[:, -1, :])
     # ESS/s legs, independent of the driver's --steps/--warmup.  The chains start from N(0,1) draws and the posterior is 7e-4 wide:
     # they need a few hundred iterations to get there, and a static L=32 trajectory is ~5 periods of this posterior long, so a
     # chain's draws are strongly autocorrelated.  With DefaultConfig's adapted diagonal mass R-hat = sqrt(1 + (tau - 1) / n) has

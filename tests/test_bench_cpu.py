@@ -103,3 +103,21 @@ def test_configs_block_runs_each_leg_as_a_watchdogged_child_and_survives_a_leg_t
     seen.clear()
     out = bench.all_configs(budget_s=0.0)
     assert not seen and all("skipped" in v for v in out.values())
+
+
+def test_dump_outputs_writes_the_last_step_s_draws_within_64_mb(tmp_path, monkeypatch):
+    """--dump-outputs DIR: the draws of the last timed iteration as DIR/draws.npy (float64); beyond the cap a seeded sample of the chains,
+    in chain order and the same in every run, so that two builds can be compared output for output."""
+    import numpy as np
+    import bench
+    small = np.random.default_rng(1).normal(size=(1024, 5))
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(tmp_path / "a" / "draws.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100 * 5 * 8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), small)
+    b, c = np.load(tmp_path / "b" / "draws.npy"), np.load(tmp_path / "c" / "draws.npy")
+    assert b.shape == (100, 5) and b.nbytes <= bench.DUMP_MAX_BYTES and np.array_equal(b, c)
+    rows = [int(np.flatnonzero((small == r).all(axis=1))[0]) for r in b]
+    assert rows == sorted(set(rows))

@@ -10,8 +10,8 @@ and runs under the mask of the region that just ended: lanes that skipped the re
 lanes are never written.  Seen in rh_chain_kernel of hier_negbin(6, 7): the 6-row prior target's loop exit spills four chain-state
 vectors with 6 lanes active (profiles/r4_spill_rootcause/).
 
-What is flagged, per basic block (label to label, labels = branch targets): a vector instruction that writes vector registers or
-memory and precedes an `s_or_b64 exec, exec, <sgpr pair>` with no other write of EXEC in between in that block -- when the block is
+What is flagged, per basic block (opened, as in the engine, by a label = branch target and behind every branch and program end): a
+vector instruction that writes vector registers or memory and precedes an `s_or_b64 exec, exec, <sgpr pair>` with no other write of EXEC in between in that block -- when the block is
 proven to be the join block of the region that restore closes (see check_lines).  The engine applies the same rule to the machine
 code itself before it launches a kernel (csrc/isacheck.cpp); this tool is the independent second statement of it, over
 llvm-objdump's text, that the CPU suite compares the engine's verdicts with.
@@ -30,6 +30,7 @@ _VECTOR = re.compile(r"^(v_|ds_|scratch_|global_|flat_|buffer_|tbuffer_|image_)"
 _EXEC_IGNORING = re.compile(r"^(v_readlane_b32|v_writelane_b32|v_readfirstlane_b32)\b")   # v_readfirstlane reads EXEC but writes an SGPR
 _END_CF = re.compile(r"^s_or_b64 exec, exec, s\[\d+:\d+\]")
 _EXEC_WRITE = re.compile(r"^s_\w+ (exec\b|s\[\d+:\d+\], .*)")
+_BLOCK_END = re.compile(r"^s_(branch|cbranch_\w+|setpc_b64|endpgm|rfe_b64)\b")
 
 
 def disassemble(path):
@@ -52,6 +53,7 @@ def check_lines(lines, strict=False):
     bodies that end in the restore)."""
     blocks = []          # (kernel, label, [instructions])
     kernel = None
+    cut = False          # the previous instruction ends its block (the engine's leaders: behind every branch and program end)
     for ln in lines:
         m = _LABEL.match(ln)
         if m:
@@ -59,11 +61,16 @@ def check_lines(lines, strict=False):
             if not re.match(r"^L\d+$", name):
                 kernel = name
             blocks.append((kernel, name, []))
+            cut = False
             continue
         if ln.startswith("\t") and blocks:
             ins = ln.strip().split("//")[0].strip()
             if ins:
+                if cut:   # an unlabelled block: e.g. the target of a long branch (s_getpc / s_setpc), which objdump does not symbolise
+                    addr = re.search(r"// ([0-9A-F]+):", ln)
+                    blocks.append((kernel, "0x%x" % int(addr.group(1), 16) if addr else "?", []))
                 blocks[-1][2].append(ins)
+                cut = bool(_BLOCK_END.match(ins))
     # witnesses: label -> set of pairs for which the label is a proven join block
     joins = {}
     for bi, (kern, lab, body) in enumerate(blocks):
