@@ -14,6 +14,11 @@
            torch never initialises its own bundled HIP runtime beside the engine's.
 
 Synthetic data (numpy default_rng(20260925)); inputs resident in HBM before the timed region starts.
+
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure needs and no more: set-up, the W warm-up steps, the K timed
+steps, `--dump-outputs`, the result line (its `roofline` comes from the timed steps' own HIP events).  `--full` adds every figure that takes
+a run of its own -- the two ESS/s legs, `roofline.traffic` measured under rocprofv3, the `configs` block (the other BASELINE
+configurations), `gpu_inlined`, `cpu_baseline` -- to the same line; the `--no-*` switches drop single ones of them from a `--full` run.
 """
 import argparse
 import ctypes as C
@@ -416,7 +421,11 @@ def all_configs(budget_s=600.0, long_legs=False):
     return out
 
 
-def main():
+FULL_RUN_S = 600.0         # a `--full` run is to end within this many seconds ...
+FULL_TAIL_S = 120.0        # ... of which the legs behind the `configs` block (gpu_inlined, cpu_baseline) take about this many
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64, help="timed HMC iterations (one step = one iteration of all chains)")
@@ -425,6 +434,9 @@ def main():
     ap.add_argument("--chains-per-gpu", type=int, default=1024)
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--leapfrog", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, everything that takes runs of its own: the ESS/s legs, roofline.traffic under rocprofv3, "
+                         "the `configs` block, gpu_inlined and cpu_baseline (~8 minutes); each --no-* switch below drops one of them again")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ess", action="store_true", help="skip the two ESS/s legs (profiling runs)")
     ap.add_argument("--no-inlined", action="store_true", help="skip the gpu_inlined leg")
@@ -458,9 +470,17 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write the last timed iteration's draw of every chain to DIR/draws.npy (float64, "
                          "[chains][parameters], at most 64 MB: a fixed, seeded sample of the chains beyond that)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if not a.full:     # a plain run: the headline figure and what the timed steps themselves yield, nothing that runs beside them
+        a.no_ess = a.no_live_traffic = a.no_configs = a.no_inlined = a.no_cpu_baseline = True
+    return a
+
+
+def main():
+    t_run = time.perf_counter()
+    a = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -626,8 +646,10 @@ def main():
         else:
             out["roofline"]["traffic_source"] = "none: profiles/%s was taken on different kernel source or workload (sha16 %s vs %s)" % (
                 TRAFFIC_PROFILE, pj.get("generated_source_sha16"), src_sha)
-    if not a.no_configs and world == 1 and dist is None:   # (a plain `python bench.py` run; not under torch.distributed.run)
-        out["configs"] = all_configs(budget_s=1100.0 if a.long_configs else 600.0, long_legs=a.long_configs)
+    if not a.no_configs and world == 1 and dist is None:   # (started as `python bench.py --full`, not under torch.distributed.run)
+        # (the default legs need ~5 minutes; they get what the run so far has left of FULL_RUN_S, so that a slow box skips a leg and says so)
+        left = FULL_RUN_S - FULL_TAIL_S - (time.perf_counter() - t_run)
+        out["configs"] = all_configs(budget_s=1100.0 if a.long_configs else min(600.0, left), long_legs=a.long_configs)
     if not a.no_inlined and world == 1:
         out["gpu_inlined"] = gpu_inlined(R, models, local_rank, L)
     if not a.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only

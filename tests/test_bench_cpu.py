@@ -105,6 +105,21 @@ def test_configs_block_runs_each_leg_as_a_watchdogged_child_and_survives_a_leg_t
     assert not seen and all("skipped" in v for v in out.values())
 
 
+def test_a_plain_run_measures_the_headline_alone_and_full_brings_the_other_legs_back():
+    """Without --full every leg that takes a run of its own is off (ESS legs, in-run traffic, `configs`, gpu_inlined, cpu_baseline); with it
+    they run as before and each --no-* switch still drops its own.  --steps / --warmup mean the same either way."""
+    import bench
+    legs = ("no_ess", "no_live_traffic", "no_configs", "no_inlined", "no_cpu_baseline")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and all(getattr(plain, k) for k in legs)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and not any(getattr(full, k) for k in legs)
+    assert (plain.steps, plain.warmup, plain.dump_outputs) == (full.steps, full.warmup, full.dump_outputs) == (20, 5, None)
+    some = bench.parse_args(["--full", "--no-cpu-baseline", "--no-configs"])
+    assert [getattr(some, k) for k in legs] == [False, False, True, False, True]
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
 def test_dump_outputs_writes_the_last_step_s_draws_within_64_mb(tmp_path, monkeypatch):
     """--dump-outputs DIR: the draws of the last timed iteration as DIR/draws.npy (float64); beyond the cap a seeded sample of the chains,
     in chain order and the same in every run, so that two builds can be compared output for output."""

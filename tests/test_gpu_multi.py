@@ -105,7 +105,8 @@ def test_rccl_all_gather_of_device_draws_world_size_one():
 
 def test_bench_under_torch_distributed_run_one_rank():
     """bench.py exactly as the driver launches it for N > 1 (`python -m torch.distributed.run ... bench.py --gpus N`), with one
-    rank: gloo bootstrap + the engine's RCCL all-gather inside the timed region; ONE JSON line on stdout."""
+    rank: gloo bootstrap + the engine's RCCL all-gather inside the timed region; ONE JSON line on stdout.  `--full`: the ESS legs, the
+    in-run traffic measurement and gpu_inlined run here too, as they do at N = 1."""
     import json
     import subprocess
     import sys
@@ -113,8 +114,8 @@ def test_bench_under_torch_distributed_run_one_rank():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
-           "--chains-per-gpu", "64", "--rows", "100000"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full",
+           "--no-cpu-baseline", "--chains-per-gpu", "64", "--rows", "100000"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port)))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
