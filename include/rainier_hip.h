@@ -38,7 +38,8 @@ extern "C" {
                              3: rh_density_eval_ex, rh_sample_multi, rh_comm_* (RCCL all-gather of the draws);
                              4: rh_model_clone;
                              5: rh_model_engines, rh_compile_count;
-                             6: rh_timing.chain_slots / steady_* (the tick engine's gradient launches serve the live chains only) */
+                             6: rh_timing.chain_slots / steady_* (the tick engine's gradient launches serve the live chains only);
+                                (still 6, additions only: rh_sampler_diagnostics, rh_diagnostics_device) */
 
 enum rh_status {
   RH_OK = 0,
@@ -288,8 +289,19 @@ int rh_optimize(rh_model *m, const double *x0, int32_t starts, int32_t max_evals
                 int32_t *status_out);
 
 /* ---- Trace.diagnostics --------------------------------------------------------------------------
- * draws [chains][iterations][nvars] (host) -> rhat [nvars], ess [nvars]   (core/Trace.scala:52-120) */
+ * draws [chains][iterations][nvars] (host) -> rhat [nvars], ess [nvars]   (core/Trace.scala:52-120)
+ * One host thread over a host copy: for draws that live on the device use the device form below, which does not move them. */
 int rh_diagnostics(const double *draws, int32_t chains, int32_t iterations, int32_t nvars, double *rhat, double *ess);
+/* Trace.diagnostics (+ the pooled mean and Trace's v) over iterations [first, first+count) of the sampler's own draws,
+ * computed on the device; rhat/ess [nvars]; mean/var [nvars] or NULL.  count <= iterations completed - first.
+ * mean = meanMean, var = v of Trace.scala:69,85: sqrt(var / ess) is the Monte-Carlo standard error of the pooled mean.
+ * Fixed-order sums: the same window gives the same bits on every call, and the bits of a copy of its rows.  The launches go
+ * to the sampler's stream behind its pending work and are not part of rh_timing.  Without a device: RH_E_DEVICE. */
+int rh_sampler_diagnostics(rh_sampler *s, int32_t first, int32_t count, double *rhat, double *ess, double *mean, double *var);
+/* the same over any device buffer of layout [chains][iterations][nvars] on `device` (-1: the current one), e.g.
+ * rh_comm_allgather_draws' *dev_out */
+int rh_diagnostics_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars,
+                          int32_t first, int32_t count, double *rhat, double *ess, double *mean, double *var);
 
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */

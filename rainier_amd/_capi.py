@@ -28,7 +28,7 @@ EXPORTS = [
     "rh_model_engines", "rh_compile_count",
     "rh_density_eval", "rh_density_eval_ex", "rh_config_default", "rh_sample", "rh_sample_multi", "rh_sampler_create", "rh_sampler_destroy",
     "rh_sampler_warmup", "rh_sampler_run", "rh_sampler_draws", "rh_sampler_draws_device", "rh_sampler_stats",
-    "rh_sampler_timing", "rh_sampler_progress", "rh_sampler_mass_dense", "rh_optimize", "rh_diagnostics", "rh_abi_version", "rh_device_count", "rh_requirements_eval",
+    "rh_sampler_timing", "rh_sampler_progress", "rh_sampler_mass_dense", "rh_optimize", "rh_diagnostics", "rh_sampler_diagnostics", "rh_diagnostics_device", "rh_abi_version", "rh_device_count", "rh_requirements_eval",
     "rh_comm_unique_id", "rh_comm_create", "rh_comm_destroy", "rh_comm_allgather_draws", "rh_comm_allreduce_max", "rh_device_synchronize",
 ]
 
@@ -108,6 +108,9 @@ def lib():
     L.rh_sampler_timing.argtypes = [vp, C.POINTER(Timing), C.c_int]
     L.rh_sampler_progress.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rh_diagnostics.argtypes = [dp, C.c_int32, C.c_int32, C.c_int32, dp, dp]
+    L.rh_sampler_diagnostics.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp]
+    L.rh_diagnostics_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp]
+    L.rh_trace_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_requirements_eval.argtypes = [vp, C.c_size_t, C.POINTER(CompileOpts), dp, C.c_int64, dp]
     L.rh_comm_unique_id.argtypes = [C.c_char_p]
     L.rh_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
@@ -237,6 +240,18 @@ def lower_only(rir: bytes, opts: CompileOpts = None, arch: str = "gfx950", colum
         L.rh_free(src)
     check(rc)
     return text, size.value
+
+
+def trace_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_trace.hip.h (Trace.diagnostics on the device) -> code object for `arch`, without a device: compiled through
+    the kernel cache and judged as before a launch (no spills, no scratch, isacheck).  Returns the code object."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_trace_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
 
 
 def lower_report(rir: bytes, opts: CompileOpts = None, arch: str = "gfx950", columns=None, nrows=None):

@@ -43,6 +43,9 @@ static const char *kPreludeSrc =
 static const char *kEngineSrc =
 #include "gen/rh_engine.inc"
     ;
+static const char *kTraceSrc =   // Trace.diagnostics on the device: model-independent, a code object of its own
+#include "gen/rh_trace.inc"
+    ;
 namespace {
 thread_local std::string g_err;
 std::atomic<long> g_compiles{0};   // hiprtc compilations of this process (cache misses): rh_compile_count
@@ -402,8 +405,11 @@ std::string cache_path(const std::string &arch, const std::string &source, const
   std::snprintf(name, sizeof name, "/%016llx", (unsigned long long)h);
   return cache_dir() + name;
 }
-std::vector<char> build_source(const std::string &arch, const std::string &source, const std::string &extra = std::string()) {
-  const std::string path = cache_path(arch, source, extra) + ".hsaco";
+// suffix: ".hsaco" for a model's code object; the model-independent ones (rh_trace.hip.h) are kept apart under a name of their own,
+// so that what sweeps the cache's *.hsaco files (the census of GENERATED control flow, tools/unproven_census.py) sees models only
+std::vector<char> build_source(const std::string &arch, const std::string &source, const std::string &extra = std::string(),
+                               const char *suffix = ".hsaco") {
+  const std::string path = cache_path(arch, source, extra) + suffix;
   std::vector<char> code;
   if (!std::getenv("RH_NO_KERNEL_CACHE") && read_file(path, code)) return code;
   std::string log;
@@ -2319,4 +2325,127 @@ extern "C" int rh_diagnostics(const double *draws, int32_t chains, int32_t itera
     ess[p] = n * m / (1 + (2 * acc));
   }
   return RH_OK;
+}
+
+// ---- Trace.diagnostics over device-resident draws (device/rh_trace.hip.h) ------------------------------------------------
+// The host form above needs the draws on the host and one thread; this one leaves them where the sampler (or the RCCL gather) put
+// them.  One code object per architecture, cached on disk like a model's, inspected by kernel_health before its first launch.
+namespace {
+const int kTraceTile = 16, kTraceSlots = 101, kTraceBlock = 256, kTraceFinBlock = 128;   // RT_TP, RT_SL, RT_BLOCK, RT_FIN_BLOCK
+const long long kTraceWsCap = 128ll << 20;                                               // RT_WS_CAP_BYTES
+struct TraceKernels { hipModule_t module = nullptr; hipFunction_t k_chain = nullptr, k_finish = nullptr; };
+std::mutex g_trace_mu;
+std::map<int, TraceKernels> g_trace;   // by device ordinal (a module belongs to its device's context; kept for the process)
+
+std::vector<char> trace_code(const std::string &arch) {
+  const std::vector<char> code = build_source(arch, std::string("// generated by rainier-hip: trace diagnostics\n") + kTraceSrc, std::string(), ".trace.co");
+  for (const char *k : {"rh_trace_chain_kernel", "rh_trace_finish_kernel"}) {
+    std::string why;
+    if (kernel_health(code, k, &why) != KH_OK) throw Fail{RH_E_UNSUPPORTED, "the trace kernels are not fit to run on this toolchain: " + (why.empty() ? std::string(k) + " is missing" : why)};
+    rh::KernelMeta km;
+    if (!rh::kernel_meta(code, k, km) || km.vgpr_spills != 0 || km.scratch_bytes != 0 || rh::kernel_touches_scratch(code, k) != 0)
+      throw Fail{RH_E_UNSUPPORTED, std::string(k) + ": spilled registers or scratch memory"};
+  }
+  return code;
+}
+const TraceKernels &trace_kernels(int dev) {
+  std::lock_guard<std::mutex> lk(g_trace_mu);
+  TraceKernels &t = g_trace[dev];
+  if (t.k_chain) return t;
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, dev));
+  std::string arch = prop.gcnArchName;
+  if (arch.find(':') != std::string::npos) arch = arch.substr(0, arch.find(':'));
+  const std::vector<char> code = trace_code(arch);
+  HIPCHK(hipModuleLoadData(&t.module, code.data()));
+  HIPCHK(hipModuleGetFunction(&t.k_finish, t.module, "rh_trace_finish_kernel"));
+  HIPCHK(hipModuleGetFunction(&t.k_chain, t.module, "rh_trace_chain_kernel"));
+  return t;
+}
+
+// the argument rules shared by the two entry points (before any device call, so that they hold on a machine without one)
+int trace_check_args(const char *fn, const void *draws, int32_t chains, int32_t iterations, int32_t nvars, int32_t first, int32_t count,
+                     const double *rhat, const double *ess) {
+  if (!draws || !rhat || !ess) { g_err = std::string(fn) + ": NULL argument"; return RH_E_INVALID; }
+  if (nvars < 1 || iterations < 0 || first < 0 || count < 2 || (int64_t)first + count > iterations) {
+    g_err = std::string(fn) + ": the window [first, first + count) must hold at least 2 of the completed iterations";
+    return RH_E_INVALID;
+  }
+  if (chains < 2) { g_err = "requirement failed: diagnostics requires multiple chains"; return RH_E_INVALID; }  // Trace.scala:12
+  return RH_OK;
+}
+
+// draws: device pointer on `dev`, [chains][iterations][nvars]; the launches go to `stream` and are waited for
+void trace_run(const void *draws, int dev, hipStream_t stream, int chains, long long iterations, int nvars, int first, int count,
+               double *rhat, double *ess, double *mean, double *var) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Fail{RH_E_DEVICE, "no HIP device available: the engine has no CPU fallback"};
+  if (dev < 0) HIPCHK(hipGetDevice(&dev));
+  if (dev >= ndev) throw Fail{RH_E_INVALID, "no such device"};
+  HIPCHK(hipSetDevice(dev));
+  const TraceKernels &K = trace_kernels(dev);
+  // parameters per chunk: the workspace [chunk][chains][RT_SL] stays under the cap; whole tiles where a tile fits
+  long long pc = kTraceWsCap / ((long long)chains * kTraceSlots * (long long)sizeof(double));
+  pc = std::max<long long>(1, std::min<long long>(pc, nvars));
+  if (pc >= kTraceTile) pc -= pc % kTraceTile;
+  DevBuf ws(sizeof(double) * (size_t)pc * chains * kTraceSlots), res(sizeof(double) * 4 * (size_t)nvars);
+  double *d_rhat = (double *)res.p, *d_ess = d_rhat + nvars, *d_mean = d_ess + nvars, *d_var = d_mean + nvars;
+  const double *d_draws = (const double *)draws;
+  double *d_ws = (double *)ws.p;
+  long long nv = nvars;
+  for (long long p0 = 0; p0 < nvars; p0 += pc) {
+    int p_lo = (int)p0, p_cnt = (int)std::min<long long>(pc, nvars - p0);
+    const long long tiles = (p_cnt + kTraceTile - 1) / kTraceTile;
+    if (tiles * chains > 0x7fffffffll) throw Fail{RH_E_UNSUPPORTED, "rh_diagnostics_device: too many chains for one launch"};
+    void *a1[] = {&d_draws, &iterations, &nv, &first, &count, &chains, &p_lo, &p_cnt, &d_ws};
+    launch(K.k_chain, (unsigned)(tiles * chains), kTraceBlock, stream, a1);
+    void *a2[] = {&d_ws, &chains, &count, &p_lo, &d_rhat, &d_ess, &d_mean, &d_var};
+    launch(K.k_finish, (unsigned)p_cnt, kTraceFinBlock, stream, a2);
+  }
+  std::vector<double> host(4 * (size_t)nvars);
+  HIPCHK(hipMemcpyAsync(host.data(), res.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  std::memcpy(rhat, host.data(), sizeof(double) * nvars);
+  std::memcpy(ess, host.data() + nvars, sizeof(double) * nvars);
+  if (mean) std::memcpy(mean, host.data() + 2 * (size_t)nvars, sizeof(double) * nvars);
+  if (var) std::memcpy(var, host.data() + 3 * (size_t)nvars, sizeof(double) * nvars);
+}
+}  // namespace
+
+extern "C" int rh_sampler_diagnostics(rh_sampler *s, int32_t first, int32_t count, double *rhat, double *ess, double *mean, double *var) {
+  if (!s) { g_err = "rh_sampler_diagnostics: NULL"; return RH_E_INVALID; }
+  const int rc0 = trace_check_args("rh_sampler_diagnostics", s->d_draws ? s->d_draws : (const void *)s, s->chains, s->it_done,
+                                   (int32_t)s->m->prog.n_params, first, count, rhat, ess);
+  if (rc0 != RH_OK) { s->m->err = g_err; return rc0; }
+  std::lock_guard<std::mutex> lk(s->m->mu);
+  // on the sampler's own stream, behind whatever it still has in flight; not part of rh_timing's figures (no events, no counters)
+  return guard(s->m, [&] {
+    trace_run(s->d_draws, s->m->device, s->m->stream, s->chains, s->cfg.iterations, (int)s->m->prog.n_params, first, count, rhat, ess, mean, var);
+  });
+}
+
+extern "C" int rh_diagnostics_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars,
+                                     int32_t first, int32_t count, double *rhat, double *ess, double *mean, double *var) {
+  const int rc0 = trace_check_args("rh_diagnostics_device", dev_draws, chains, iterations, nvars, first, count, rhat, ess);
+  if (rc0 != RH_OK) return rc0;
+  return guard(nullptr, [&] {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Fail{RH_E_DEVICE, "no HIP device available: the engine has no CPU fallback"};
+    if (device < 0) HIPCHK(hipGetDevice(&device));
+    if (device >= ndev) throw Fail{RH_E_INVALID, "rh_diagnostics_device: no such device"};
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());   // whoever filled the buffer (a sampler's stream, the RCCL gather) has finished
+    trace_run(dev_draws, device, nullptr, chains, iterations, nvars, first, count, rhat, ess, mean, var);
+  });
+}
+
+// No device needed: device/rh_trace.hip.h -> code object for `arch` (through the kernel cache), judged as before a launch.
+// *code_out: the code object (malloc'ed, the caller frees it with rh_free).  build() calls it so that the code object is in the
+// in-tree kernel cache; the CPU tests read the kernels' metadata from it.
+extern "C" int rh_trace_lower_only(const char *arch, void **code_out, size_t *code_size) {
+  return guard(nullptr, [&] {
+    const std::vector<char> code = trace_code(arch && *arch ? arch : "gfx950");
+    if (code_size) *code_size = code.size();
+    if (code_out) { *code_out = std::malloc(code.size()); std::memcpy(*code_out, code.data(), code.size()); }
+  });
 }

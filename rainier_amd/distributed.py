@@ -65,6 +65,15 @@ class Comm:
         _capi.check(_capi.lib().rh_comm_allgather_draws(self._h, sampler._h, None, C.byref(p)))
         return p.value
 
+    def diagnostics(self, sampler, first: int = 0, count=None, moments: bool = False):
+        """collective: Trace.diagnostics over the chains of ALL ranks -- one all-gather that stays on the device, analysed there
+        (rh_diagnostics_device); every rank gets the same list of (rHat, effectiveSampleSize) as Sampler.diagnostics gives for its own"""
+        from .sampler import diagnostics_device
+        count = sampler.progress()[1] - int(first) if count is None else int(count)
+        ptr = self.allgather_draws(sampler, to_host=False)
+        return diagnostics_device(ptr, self.world * sampler.chains, sampler.iterations, sampler.model.nVars, device=self.device,
+                                  first=first, count=count, moments=moments)
+
     def allreduce_max(self, v: float) -> float:
         a = np.array([float(v)])
         _capi.check(_capi.lib().rh_comm_allreduce_max(self._h, _capi.dptr(a)))

@@ -216,6 +216,23 @@ def diagnostics(chains: np.ndarray):
     return list(zip(rhat.tolist(), ess.tolist()))
 
 
+def _diag_result(rhat, ess, mean, var, moments):
+    diag = list(zip(rhat.tolist(), ess.tolist()))
+    return (diag, mean, var) if moments else diag
+
+
+def diagnostics_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0,
+                       count: Optional[int] = None, moments: bool = False):
+    """Trace.diagnostics over a device buffer [chains][iterations][nvars] (a sampler's draws, Comm.allgather_draws(to_host=False)),
+    computed where the draws are: the list of (rHat, effectiveSampleSize) over iterations [first, first + count); with moments
+    also the pooled mean and Trace's v per parameter (sqrt(v / ess) = the Monte-Carlo standard error of the mean)."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    rhat, ess, mean, var = (np.zeros(nvars) for _ in range(4))
+    _capi.check(_capi.lib().rh_diagnostics_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count,
+                                                  _capi.dptr(rhat), _capi.dptr(ess), _capi.dptr(mean), _capi.dptr(var)))
+    return _diag_result(rhat, ess, mean, var, moments)
+
+
 def predict(requirements_rir: bytes, draws: np.ndarray, n_requirements: int, device: int = -1,
             math_mode: int = _capi.MATH_FAST) -> np.ndarray:
     """Trace.predict's compiled part (core/Trace.scala:34-41, core/Generator.scala:59-94): evaluate the requirements
@@ -275,6 +292,17 @@ class Sampler:
         w, it = C.c_int32(0), C.c_int32(0)
         _capi.check(_capi.lib().rh_sampler_progress(self._h, C.byref(w), C.byref(it)), self.model._h)
         return bool(w.value), int(it.value)
+
+    def diagnostics(self, first: int = 0, count: Optional[int] = None, moments: bool = False):
+        """Trace.diagnostics of the draws where they are (rh_sampler_diagnostics): the list of (rHat, effectiveSampleSize) per
+        parameter over iterations [first, first + count), count = None: everything completed so far; with moments = True
+        (diag, mean [nVars], var [nVars]) -- the pooled mean and Trace's v."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        n = self.model.nVars
+        rhat, ess, mean, var = (np.zeros(n) for _ in range(4))
+        _capi.check(_capi.lib().rh_sampler_diagnostics(self._h, int(first), count, _capi.dptr(rhat), _capi.dptr(ess), _capi.dptr(mean),
+                                                       _capi.dptr(var)), self.model._h)
+        return _diag_result(rhat, ess, mean, var, moments)
 
     def mass_dense(self) -> np.ndarray:
         """DenseMassMatrix.elements of every chain: [chains][nVars][nVars] (DenseMassMatrixTuner only)."""
