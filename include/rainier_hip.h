@@ -303,6 +303,30 @@ int rh_sampler_diagnostics(rh_sampler *s, int32_t first, int32_t count, double *
 int rh_diagnostics_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars,
                           int32_t first, int32_t count, double *rhat, double *ess, double *mean, double *var);
 
+/* ---- Trace.predict / Trace.thin over device-resident draws (core/Trace.scala:23-41, core/Generator.scala:59-94) ----
+ * rh_requirements_eval above takes host draws and compiles on every call.  A predictor is the same requirements program
+ * (header kind 1) compiled ONCE for one device -- through the kernel cache, and judged like a model's kernels before it may be
+ * launched (no spilled registers, no scratch, the static code check): a program whose kernels fail returns RH_E_UNSUPPORTED
+ * with the reason -- and evaluated where the draws are (csrc/device/rh_predict.hip.h).
+ * Window and thinning: the kept iterations are first + j*thin, j = 0 .. ceil(count/thin)-1 (Trace.thin keeps i % n == 0,
+ * applied to the window); first >= 0, count >= 1, thin >= 1, first + count <= iterations (completed, for a sampler).
+ * Result layout [chains][kept][nreq] -- the layout rh_diagnostics_device reads, so R-hat / ESS of a prediction is one more call
+ * on *dev_out.  host_out (may be NULL): caller-allocated; *dev_out (may be NULL): the handle's own device buffer, valid until
+ * the next predict call on this handle or rh_predict_destroy.  Later calls compile nothing.  With fp_contract = 0 every value
+ * has the bits rh_requirements_eval gives for the same row and opts.  An out-of-range Lookup: RH_E_LOOKUP.  No device:
+ * RH_E_DEVICE (no CPU fallback).  Handle, sampler or buffer on different devices, a broken window, another nvars: RH_E_INVALID. */
+typedef struct rh_predict rh_predict;
+int rh_predict_create(const void *rir, size_t rir_len, const rh_compile_opts *opts, rh_predict **out);
+void rh_predict_destroy(rh_predict *p);
+int rh_predict_nreq(const rh_predict *p);
+int rh_predict_nvars(const rh_predict *p);
+/* over the sampler's own draws, on its stream behind its pending work; not part of rh_timing; the chains are not altered */
+int rh_sampler_predict(rh_sampler *s, rh_predict *p, int32_t first, int32_t count, int32_t thin, double *host_out, void **dev_out);
+/* over any device buffer [chains][iterations][nvars] on `device` (-1: the handle's), e.g. rh_comm_allgather_draws' *dev_out;
+ * synchronises the device before and after */
+int rh_predict_device(rh_predict *p, const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars,
+                      int32_t first, int32_t count, int32_t thin, double *host_out, void **dev_out);
+
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */
 int rh_device_count(void);

@@ -6,6 +6,6 @@
   models.py        the BASELINE.json configurations as RIR + synthetic data
 """
 from .sampler import (DefaultConfig, DenseMassMatrixTuner, DensityFunction, DiagonalMassMatrix, DiagonalMassMatrixTuner,  # noqa: F401
-                      DualAvgTuner, EHMC, EHMCSampler, HMC, HMCSampler, IdentityMassMatrixTuner, Model, NUTSSampler,
+                      DualAvgTuner, EHMC, EHMCSampler, HMC, HMCSampler, IdentityMassMatrixTuner, Model, NUTSSampler, Predictor,
                       RainierHipError, Sampler, SamplerConfig, StaticMassMatrix, StaticStepSize, Trace,
-                      diagnostics, diagnostics_device, make_config, predict, sample_multi)
+                      diagnostics, diagnostics_device, make_config, predict, predict_device, sample_multi)

@@ -30,6 +30,8 @@ EXPORTS = [
     "rh_sampler_warmup", "rh_sampler_run", "rh_sampler_draws", "rh_sampler_draws_device", "rh_sampler_stats",
     "rh_sampler_timing", "rh_sampler_progress", "rh_sampler_mass_dense", "rh_optimize", "rh_diagnostics", "rh_sampler_diagnostics", "rh_diagnostics_device", "rh_abi_version", "rh_device_count", "rh_requirements_eval",
     "rh_comm_unique_id", "rh_comm_create", "rh_comm_destroy", "rh_comm_allgather_draws", "rh_comm_allreduce_max", "rh_device_synchronize",
+    # Trace.predict / Trace.thin over device-resident draws (core/Trace.scala:23-41, core/Generator.scala:59-94)
+    "rh_predict_create", "rh_predict_destroy", "rh_predict_nreq", "rh_predict_nvars", "rh_sampler_predict", "rh_predict_device",
 ]
 
 
@@ -112,6 +114,13 @@ def lib():
     L.rh_diagnostics_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp]
     L.rh_trace_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_requirements_eval.argtypes = [vp, C.c_size_t, C.POINTER(CompileOpts), dp, C.c_int64, dp]
+    L.rh_predict_create.argtypes = [vp, C.c_size_t, C.POINTER(CompileOpts), C.POINTER(vp)]
+    L.rh_predict_destroy.restype = None; L.rh_predict_destroy.argtypes = [vp]
+    L.rh_predict_nreq.argtypes = [vp]
+    L.rh_predict_nvars.argtypes = [vp]
+    L.rh_sampler_predict.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(vp)]
+    L.rh_predict_device.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(vp)]
+    L.rh_lower_predict.argtypes = [vp, C.c_size_t, C.POINTER(CompileOpts), C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(vp)]
     L.rh_comm_unique_id.argtypes = [C.c_char_p]
     L.rh_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.rh_comm_destroy.argtypes = [vp]
@@ -252,6 +261,25 @@ def trace_lower_only(arch: str = "gfx950") -> bytes:
         return C.string_at(code, n.value)
     finally:
         L.rh_free(code)
+
+
+def lower_predict(rir: bytes, opts: CompileOpts = None, arch: str = "gfx950", compile: bool = True):
+    """A requirements program -> the source rh_predict_create compiles (csrc/device/rh_predict.hip.h behind the generated
+    rh_pred_eval) and its code object for `arch`, without a device: through the kernel cache, judged as before a launch (no spills,
+    no scratch, isacheck).  Returns (source, code object); compile = False stops after the lowering (code object b"")."""
+    L = lib()
+    src, code, n = C.c_char_p(), C.c_void_p(), C.c_size_t(0)
+    buf = C.create_string_buffer(rir, len(rir))
+    o = opts if opts is not None else compile_opts()
+    rc = L.rh_lower_predict(buf, len(rir), C.byref(o), arch.encode(), C.byref(src), C.byref(n) if compile else None, C.byref(code))
+    text = src.value.decode() if src.value else ""
+    blob = C.string_at(code, n.value) if code else b""
+    if src:
+        L.rh_free(src)
+    if code:
+        L.rh_free(code)
+    check(rc)
+    return text, blob
 
 
 def lower_report(rir: bytes, opts: CompileOpts = None, arch: str = "gfx950", columns=None, nrows=None):

@@ -189,6 +189,7 @@ struct TargetEmitter {
   uint32_t run_end = 0;        // data-free targets t..run_end are emitted together (shared sub-expressions once)
   bool merged_away = false;    // this data-free target was emitted by an earlier one of its run
   int chunk = 0;               // > 0: memory-resident lowering, at most this many statement groups per chunk (chunk_body)
+  const std::map<uint32_t, int> *pred_slot = nullptr;   // emit_predict: parameter index -> compact slot; parameter k is spelled th(slot of k)
   // memory-resident lowering: the accumulators and invariants are reached through an OPAQUE index (rh_oz() is a volatile asm that
   // yields 0), so the arrays cannot be split into registers and no load is forwarded from a store or hoisted out of the row loop
   std::string oz() const { return chunk > 0 ? " + rh_oz()" : ""; }
@@ -875,6 +876,7 @@ struct TargetEmitter {
     const Node &nd = P.nodes[id];
     if (nd.op == RH_RIR_CONST) return (pooled() && ctx == 1 && !structural(nd.cval)) ? pool_ref(nd.cval) : lit(nd.cval);
     if (nd.op == RH_RIR_INPUT) {
+      if (nd.input < P.n_params && pred_slot) return "th(" + std::to_string(pred_slot->at(nd.input)) + ")";
       if (nd.input < P.n_params) return "th[" + std::to_string(nd.input) + "]";
       return "c[" + std::to_string(nd.input - P.targets[t].input_start) + oz() + "]";   // (memory-resident lowering: the row's values stay in scratch too)
     }
@@ -913,14 +915,17 @@ struct TargetEmitter {
     // every use below compares or indexes k as unsigned
     os << "    const int " << k << " = (int)((unsigned)rh_d2i(" << R(nd.a) << ") - (unsigned)(" << nd.low << "));\n";
     auto it_tab = use_inv ? inv_table.find(id) : inv_table.end();   // (the GLM scalar part has no inv[]: it keeps its own copies)
-    bool all_params = chunk > 0 && nd.table.size() > 2;   // memory-resident lowering: theta is in memory (RH_BIGTH), so a table of parameters is ONE indexed load
+    // memory-resident lowering: theta is in memory (RH_BIGTH), so a table of parameters is ONE indexed load; emit_predict: its accessor
+    // takes a run-time slot, so a table too long for the select chain is one indexed read as well (never a per-evaluation array)
+    bool all_params = (chunk > 0 || (pred_slot && nd.table.size() > 64)) && nd.table.size() > 2;
     for (uint32_t e : nd.table) all_params = all_params && P.nodes[e].op == RH_RIR_INPUT && P.nodes[e].input < P.n_params && !(gather.ok && e == gather.node);
     if (it_tab != inv_table.end()) {
       os << lhs << "((unsigned)" << k << " < " << nd.table.size() << "u) ? inv[" << it_tab->second << " + " << k << "] : RH_NAN;\n";
     } else if (all_params) {
       os << "    static const int p" << id << "[" << nd.table.size() << "] = {";
-      for (size_t e = 0; e < nd.table.size(); e++) os << (e ? ", " : "") << P.nodes[nd.table[e]].input;
-      os << "};\n" << lhs << "((unsigned)" << k << " < " << nd.table.size() << "u) ? th[p" << id << "[" << k << "]] : RH_NAN;\n";
+      for (size_t e = 0; e < nd.table.size(); e++) os << (e ? ", " : "") << (pred_slot ? (uint32_t)pred_slot->at(P.nodes[nd.table[e]].input) : P.nodes[nd.table[e]].input);
+      if (pred_slot) os << "};\n" << lhs << "((unsigned)" << k << " < " << nd.table.size() << "u) ? th(p" << id << "[" << k << "]) : RH_NAN;\n";
+      else os << "};\n" << lhs << "((unsigned)" << k << " < " << nd.table.size() << "u) ? th[p" << id << "[" << k << "]] : RH_NAN;\n";
     } else if (nd.table.size() <= (chunk > 0 ? 4u : 64u)) {
       os << lhs;
       for (size_t e = 0; e + 1 < nd.table.size(); e++) os << "(" << k << " == " << e << ") ? " << R(nd.table[e]) << " : ";
@@ -1548,12 +1553,21 @@ bool emit_hip(const Program &P, const EmitOptions &o, std::string &defines, std:
   err.clear();
   return true;
 }
-static bool emit_requirements_impl(const Program &P, const EmitOptions &o, std::string &defines, std::string &body, std::string &err);
+static bool emit_requirements_impl(const Program &P, const EmitOptions &o, std::string &defines, std::string &body, std::string &err,
+                                   std::vector<uint32_t> *refs = nullptr);
 bool emit_requirements(const Program &P, const EmitOptions &o, std::string &defines, std::string &body, std::string &err) {
   if (!o.simplify) return emit_requirements_impl(P, o, defines, body, err);
   return emit_requirements_impl(simplify(P, o.fp_contract), o, defines, body, err);
 }
-static bool emit_requirements_impl(const Program &P, const EmitOptions &o, std::string &defines, std::string &body, std::string &err) {
+bool emit_predict(const Program &P, const EmitOptions &o, std::string &defines, std::string &body, std::string &err, std::vector<uint32_t> &refs) {
+  if (!o.simplify) return emit_requirements_impl(P, o, defines, body, err, &refs);
+  return emit_requirements_impl(simplify(P, o.fp_contract), o, defines, body, err, &refs);
+}
+// refs == nullptr: rh_req_eval(th[RH_NTH], out, err), the spelling rh_requirements_eval compiles.  refs != nullptr (emit_predict): the
+// same nodes in the same order with the same expression text, but parameter k is read as th(slot of k) -- th any callable over the
+// compact slots -- and *refs / RH_NREF / RH_REQ_REF_INIT list the parameters the swept DAG reads, ascending (slot s <-> refs[s]).
+static bool emit_requirements_impl(const Program &P, const EmitOptions &o, std::string &defines, std::string &body, std::string &err,
+                                   std::vector<uint32_t> *refs) {
   // one shared evaluation of the union DAG (like a run of data-free targets), then out[m] = requirement m
   TargetEmitter te(P, 0, false);
   te.fast_div = o.fp_contract;
@@ -1563,10 +1577,19 @@ static bool emit_requirements_impl(const Program &P, const EmitOptions &o, std::
   te.reach_row.assign(P.nodes.size(), 0);
   for (auto &T : P.targets) te.reach_row[T.outputs[0]] = 1;
   te.sweep(te.reach_row);
+  std::map<uint32_t, int> slot;
+  if (refs) {
+    for (size_t n = 0; n < P.nodes.size(); n++)
+      if (te.reach_row[n] && te.is_param((uint32_t)n)) slot[P.nodes[n].input] = 0;
+    refs->clear();
+    for (auto &kv : slot) { kv.second = (int)refs->size(); refs->push_back(kv.first); }
+    te.pred_slot = &slot;
+  }
   std::ostringstream os;
   if (o.fp_contract) os << "#pragma clang fp contract(fast)\n";
-  os << "RH_DEV void rh_req_eval(const double (&th)[RH_NTH], double (&out)[RH_NREQ], int &err) {\n  (void)th; (void)err;\n"
-        "  const double *inv = nullptr, *c = nullptr; (void)inv; (void)c;\n";
+  if (refs) os << "template <class RH_TH> RH_DEV void rh_pred_eval(const RH_TH &th, double (&out)[RH_NREQ], int &err) {\n  (void)th; (void)err;\n";
+  else os << "RH_DEV void rh_req_eval(const double (&th)[RH_NTH], double (&out)[RH_NREQ], int &err) {\n  (void)th; (void)err;\n";
+  os << "  const double *inv = nullptr, *c = nullptr; (void)inv; (void)c;\n";
   for (size_t n = 0; n < P.nodes.size(); n++) {
     if (!te.reach_row[n] || te.trivial((uint32_t)n)) continue;
     if (!te.emit_node(os, (uint32_t)n, 1, err)) return false;
@@ -1576,6 +1599,11 @@ static bool emit_requirements_impl(const Program &P, const EmitOptions &o, std::
   body = os.str();
   std::ostringstream d;
   d << "#define RH_NVARS " << P.n_params << "\n#define RH_NTH " << P.n_params << "\n#define RH_SLOTS " << ((P.n_params + 63) / 64) << "\n#define RH_NREQ " << P.targets.size() << "\n";
+  if (refs) {
+    d << "#define RH_NREF " << refs->size() << "\n#define RH_REQ_REF_INIT {";
+    for (size_t s = 0; s < refs->size(); s++) d << (s ? ", " : "") << (*refs)[s];
+    d << (refs->empty() ? "0}\n" : "}\n");
+  }
   if (o.strict_math) d << "#define RH_EXP(x) rh_strict_exp(x)\n#define RH_LOG(x) rh_strict_log(x)\n";
   else d << "#define RH_EXP(x) exp(x)\n#define RH_LOG(x) " << (o.fast_log ? "rh_fast_log(x)" : "log(x)") << "\n";
   defines = d.str();

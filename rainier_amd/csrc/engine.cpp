@@ -46,6 +46,9 @@ static const char *kEngineSrc =
 static const char *kTraceSrc =   // Trace.diagnostics on the device: model-independent, a code object of its own
 #include "gen/rh_trace.inc"
     ;
+static const char *kPredictSrc =   // Trace.predict on the device: follows the generated rh_pred_eval of one requirements program
+#include "gen/rh_predict.inc"
+    ;
 namespace {
 thread_local std::string g_err;
 std::atomic<long> g_compiles{0};   // hiprtc compilations of this process (cache misses): rh_compile_count
@@ -2447,5 +2450,202 @@ extern "C" int rh_trace_lower_only(const char *arch, void **code_out, size_t *co
     const std::vector<char> code = trace_code(arch && *arch ? arch : "gfx950");
     if (code_size) *code_size = code.size();
     if (code_out) { *code_out = std::malloc(code.size()); std::memcpy(*code_out, code.data(), code.size()); }
+  });
+}
+
+// ---- Trace.predict / Trace.thin over device-resident draws (device/rh_predict.hip.h) ---------------------------------------------
+// rh_requirements_eval above uploads host draws and compiles on every call; a predictor is compiled once (kernel cache), judged
+// like a model's kernels, and evaluated where the draws are.  core/Trace.scala:23-41, core/Generator.scala:59-94.
+struct rh_predict {
+  int device = 0, nreq = 0, nvars = 0, nref = 0;
+  hipModule_t module = nullptr;
+  hipFunction_t k_flat = nullptr, k_gather = nullptr, k_direct = nullptr;
+  int tile_flat = 0, tile_gather = 0, tile_direct = 0;
+  void *d_out = nullptr, *d_err = nullptr;
+  size_t out_bytes = 0;
+  std::mutex mu;
+};
+namespace {
+// device/rh_predict.hip.h: RP_WAVE, RP_MAX_TILE, RP_LDS_DOUBLES, RP_TILE_FOR
+const int kPredWave = 64, kPredMaxTile = 256, kPredLdsDoubles = 8064;
+int pred_tile_for(int stride) {
+  const int rows = kPredLdsDoubles / stride;
+  return rows >= kPredMaxTile ? kPredMaxTile : rows / kPredWave * kPredWave;
+}
+struct PredictLowered {
+  std::string src;
+  std::vector<char> code;
+  int nreq = 0, nvars = 0, nref = 0;
+  std::vector<std::string> kernels;   // the kernels the source holds, all fit to run
+};
+// RIR -> source -> code object for `arch` (kernel cache) -> every kernel judged; throws what rh_predict_create returns
+void predict_lower(const void *rir, size_t rir_len, const rh_compile_opts *opts, const std::string &arch, PredictLowered &L, bool compile) {
+  rh::Program P; std::string err;
+  if (!rh::parse_rir(rir, rir_len, P, err)) throw Fail{RH_E_INVALID, err};
+  if (P.kind != 1) throw Fail{RH_E_INVALID, "not a requirements program (header kind != 1)"};
+  if (P.targets.empty()) throw Fail{RH_E_INVALID, "a requirements program without requirements"};
+  rh::EmitOptions eo;
+  if (opts) { eo.strict_math = opts->math_mode == RH_MATH_STRICT; eo.fp_contract = opts->fp_contract != 0; }
+  std::string defines, body;
+  std::vector<uint32_t> refs;
+  if (!rh::emit_predict(P, eo, defines, body, err, refs)) throw Fail{RH_E_UNSUPPORTED, err};
+  L.nreq = (int)P.targets.size(); L.nvars = (int)P.n_params; L.nref = (int)refs.size();
+  L.src = "// generated by rainier-hip: requirements program for device-resident draws\n" + defines + kSharedSrc + "\n" + kPreludeSrc + "\n" + body + kPredictSrc;
+  const bool gather = pred_tile_for(L.nref | 1) >= kPredWave, flat = pred_tile_for(L.nvars | 1) >= kPredWave && 2 * L.nref >= L.nvars;
+  if (flat) L.kernels.push_back("rh_predict_flat_kernel");
+  if (gather) L.kernels.push_back("rh_predict_gather_kernel"); else L.kernels.push_back("rh_predict_direct_kernel");
+  if (!compile) return;
+  L.code = build_source(arch, L.src, std::string(), ".predict.co");   // (kept apart from the models' *.hsaco, like the trace kernels)
+  for (const std::string &k : L.kernels) {
+    std::string why;
+    if (kernel_health(L.code, k, &why) != KH_OK)
+      throw Fail{RH_E_UNSUPPORTED, "the predict kernel is not fit to run: " + (why.empty() ? k + " is missing" : why)};
+    rh::KernelMeta km;
+    if (!rh::kernel_meta(L.code, k, km) || km.vgpr_spills != 0 || km.sgpr_spills != 0 || km.scratch_bytes != 0 || rh::kernel_touches_scratch(L.code, k) != 0)
+      throw Fail{RH_E_UNSUPPORTED, "the predict kernel is not fit to run: " + k + ": spilled registers or scratch memory"};
+  }
+}
+
+// the argument rules of the two entry points (before any device call, so that they hold on a machine without one)
+int predict_check_args(const char *fn, const rh_predict *p, const void *draws, int64_t chains, int64_t iterations, int64_t nvars, int32_t first,
+                       int32_t count, int32_t thin) {
+  if (!p || !draws) { g_err = std::string(fn) + ": NULL argument"; return RH_E_INVALID; }
+  if (chains < 1 || iterations < 0 || first < 0 || count < 1 || thin < 1 || (int64_t)first + count > iterations) {
+    g_err = std::string(fn) + ": the window [first, first + count) must hold at least 1 of the completed iterations, thin >= 1";
+    return RH_E_INVALID;
+  }
+  if (nvars != p->nvars) { g_err = std::string(fn) + ": the draws have " + std::to_string(nvars) + " parameters, the program reads " + std::to_string(p->nvars); return RH_E_INVALID; }
+  return RH_OK;
+}
+
+// draws: device pointer on p's device, [chains][iterations][nvars]; the launch goes to `stream` and is waited for
+void predict_run(rh_predict *p, const void *draws, hipStream_t stream, int chains, long long iterations, int first, int count, int thin,
+                 double *host_out, void **dev_out, int *lookup_err) {
+  HIPCHK(hipSetDevice(p->device));
+  const long long kept64 = ((long long)count + thin - 1) / thin;
+  int kept = (int)kept64;
+  const size_t need = sizeof(double) * (size_t)chains * (size_t)kept * (size_t)p->nreq;
+  if (need > p->out_bytes) {
+    if (p->d_out) { HIPCHK(hipFree(p->d_out)); p->d_out = nullptr; p->out_bytes = 0; }
+    HIPCHK(hipMalloc(&p->d_out, need));
+    p->out_bytes = need;
+  }
+  const bool flat = p->k_flat && thin == 1;
+  hipFunction_t fn = flat ? p->k_flat : (p->k_gather ? p->k_gather : p->k_direct);
+  const int tile = flat ? p->tile_flat : (p->k_gather ? p->tile_gather : p->tile_direct);
+  int ntiles = (kept + tile - 1) / tile;
+  if ((long long)ntiles * chains > 0x7fffffffll) throw Fail{RH_E_UNSUPPORTED, "predict: too many chains x iterations for one launch"};
+  HIPCHK(hipMemsetAsync(p->d_err, 0, sizeof(int), stream));
+  const double *d_draws = (const double *)draws;
+  double *d_out = (double *)p->d_out;
+  int *d_err = (int *)p->d_err;
+  void *args[] = {&d_draws, &iterations, &first, &thin, &kept, &ntiles, &d_out, &d_err};
+  launch(fn, (unsigned)((long long)ntiles * chains), (unsigned)tile, stream, args);
+  if (host_out) HIPCHK(hipMemcpyAsync(host_out, p->d_out, need, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(lookup_err, p->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (dev_out) *dev_out = p->d_out;
+}
+}  // namespace
+
+extern "C" int rh_predict_create(const void *rir, size_t rir_len, const rh_compile_opts *opts, rh_predict **out) {
+  if (!rir || !out) { g_err = "rh_predict_create: NULL argument"; return RH_E_INVALID; }
+  *out = nullptr;
+  std::unique_ptr<rh_predict> p(new rh_predict);
+  const int rc = guard(nullptr, [&] {
+    PredictLowered L;
+    predict_lower(rir, rir_len, opts, "", L, false);   // the argument errors first: they hold without a device
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Fail{RH_E_DEVICE, "no HIP device available: the engine has no CPU fallback"};
+    int dev = opts ? opts->device : -1;
+    if (dev < 0) HIPCHK(hipGetDevice(&dev));
+    if (dev >= ndev) throw Fail{RH_E_INVALID, "rh_predict_create: no such device"};
+    HIPCHK(hipSetDevice(dev));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, dev));
+    std::string arch = prop.gcnArchName;
+    if (arch.find(':') != std::string::npos) arch = arch.substr(0, arch.find(':'));
+    L = PredictLowered();
+    predict_lower(rir, rir_len, opts, arch, L, true);
+    p->device = dev; p->nreq = L.nreq; p->nvars = L.nvars; p->nref = L.nref;
+    HIPCHK(hipModuleLoadData(&p->module, L.code.data()));
+    for (const std::string &k : L.kernels) {
+      hipFunction_t f;
+      HIPCHK(hipModuleGetFunction(&f, p->module, k.c_str()));
+      if (k == "rh_predict_flat_kernel") { p->k_flat = f; p->tile_flat = pred_tile_for(L.nvars | 1); }
+      else if (k == "rh_predict_gather_kernel") { p->k_gather = f; p->tile_gather = pred_tile_for(L.nref | 1); }
+      else { p->k_direct = f; p->tile_direct = kPredWave; }
+    }
+    HIPCHK(hipMalloc(&p->d_err, sizeof(int)));
+  });
+  if (rc != RH_OK) { rh_predict_destroy(p.release()); return rc; }
+  *out = p.release();
+  return RH_OK;
+}
+
+extern "C" void rh_predict_destroy(rh_predict *p) {
+  if (!p) return;
+  if (p->module || p->d_out || p->d_err) {
+    (void)hipSetDevice(p->device);
+    if (p->d_out) (void)hipFree(p->d_out);
+    if (p->d_err) (void)hipFree(p->d_err);
+    if (p->module) (void)hipModuleUnload(p->module);
+  }
+  delete p;
+}
+extern "C" int rh_predict_nreq(const rh_predict *p) { return p ? p->nreq : -1; }
+extern "C" int rh_predict_nvars(const rh_predict *p) { return p ? p->nvars : -1; }
+
+extern "C" int rh_sampler_predict(rh_sampler *s, rh_predict *p, int32_t first, int32_t count, int32_t thin, double *host_out, void **dev_out) {
+  if (!s) { g_err = "rh_sampler_predict: NULL"; return RH_E_INVALID; }
+  int rc0 = predict_check_args("rh_sampler_predict", p, s->d_draws ? s->d_draws : (const void *)s, s->chains, s->it_done, (int64_t)s->m->prog.n_params,
+                               first, count, thin);
+  if (rc0 == RH_OK && p->device != s->m->device) { g_err = "rh_sampler_predict: the predictor and the sampler are on different devices"; rc0 = RH_E_INVALID; }
+  if (rc0 != RH_OK) { s->m->err = g_err; return rc0; }
+  std::lock_guard<std::mutex> lk(s->m->mu);
+  std::lock_guard<std::mutex> lp(p->mu);
+  int lookup_err = 0;
+  // on the sampler's own stream, behind whatever it still has in flight; reads the draws only; not part of rh_timing's figures
+  const int rc = guard(s->m, [&] {
+    predict_run(p, s->d_draws, s->m->stream, s->chains, s->cfg.iterations, first, count, thin, host_out, dev_out, &lookup_err);
+  });
+  if (rc == RH_OK && lookup_err) { g_err = "Lookup index out of range during evaluation"; s->m->err = g_err; return RH_E_LOOKUP; }
+  return rc;
+}
+
+extern "C" int rh_predict_device(rh_predict *p, const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars,
+                                 int32_t first, int32_t count, int32_t thin, double *host_out, void **dev_out) {
+  int rc0 = predict_check_args("rh_predict_device", p, dev_draws, chains, iterations, nvars, first, count, thin);
+  if (rc0 == RH_OK && device >= 0 && device != p->device) { g_err = "rh_predict_device: the predictor and the buffer are on different devices"; rc0 = RH_E_INVALID; }
+  if (rc0 != RH_OK) return rc0;
+  std::lock_guard<std::mutex> lp(p->mu);
+  int lookup_err = 0;
+  const int rc = guard(nullptr, [&] {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, dev_draws) == hipSuccess && at.type == hipMemoryTypeDevice && at.device != p->device)
+      throw Fail{RH_E_INVALID, "rh_predict_device: the predictor and the buffer are on different devices"};
+    (void)hipGetLastError();
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipDeviceSynchronize());   // whoever filled the buffer (a sampler's stream, the RCCL gather) has finished
+    predict_run(p, dev_draws, nullptr, chains, iterations, first, count, thin, host_out, dev_out, &lookup_err);
+  });
+  if (rc == RH_OK && lookup_err) { g_err = "Lookup index out of range during evaluation"; return RH_E_LOOKUP; }
+  return rc;
+}
+
+// No device needed (next to rh_lower_only): a requirements program -> the predict source and its code object for `arch`, through
+// the kernel cache, judged as rh_predict_create judges it.  *src_out / *code_out: malloc'ed, freed with rh_free; code_size NULL
+// stops after the lowering.  build() calls it so that the GPU tests' predictors come from the in-tree kernel cache.
+extern "C" int rh_lower_predict(const void *rir, size_t rir_len, const rh_compile_opts *opts, const char *arch, char **src_out,
+                                size_t *code_size, void **code_out) {
+  if (src_out) *src_out = nullptr;
+  if (code_out) *code_out = nullptr;
+  if (!rir) { g_err = "rh_lower_predict: NULL argument"; return RH_E_INVALID; }
+  return guard(nullptr, [&] {
+    PredictLowered L;
+    struct Keep { PredictLowered &L; char **src_out; ~Keep() { if (src_out && !L.src.empty()) { *src_out = (char *)std::malloc(L.src.size() + 1); std::memcpy(*src_out, L.src.c_str(), L.src.size() + 1); } } } keep{L, src_out};
+    predict_lower(rir, rir_len, opts, arch && *arch ? arch : "gfx950", L, code_size != nullptr);
+    if (code_size) *code_size = L.code.size();
+    if (code_out && code_size) { *code_out = std::malloc(L.code.size()); std::memcpy(*code_out, L.code.data(), L.code.size()); }
   });
 }

@@ -174,6 +174,10 @@ bool emit_hip(const Program &p, const EmitOptions &o, std::string &defines, std:
 
 // Lowers a requirements program (kind 1) to  rh_req_eval(th, out, err)  + defines RH_NVARS / RH_NREQ.
 bool emit_requirements(const Program &p, const EmitOptions &o, std::string &defines, std::string &body, std::string &err);
+// The same program for device/rh_predict.hip.h:  rh_pred_eval(th, out, err)  reads parameter k as th(slot of k) instead of th[k] of a
+// full-length array; refs = the parameters the swept DAG reads, ascending (slot s <-> refs[s]), also spelled into `defines` as
+// RH_NREF and RH_REQ_REF_INIT (the initialiser of rh_req_ref[]).  Node order, expression text and pragmas are emit_requirements'.
+bool emit_predict(const Program &p, const EmitOptions &o, std::string &defines, std::string &body, std::string &err, std::vector<uint32_t> &refs);
 
 // ---- isacheck.cpp: what the engine reads out of a code object before it agrees to launch one of its kernels -----------------
 struct KernelMeta {

@@ -74,6 +74,23 @@ class Comm:
         return diagnostics_device(ptr, self.world * sampler.chains, sampler.iterations, sampler.model.nVars, device=self.device,
                                   first=first, count=count, moments=moments)
 
+    def predict(self, sampler_or_gathered, predictor, first: int = 0, count=None, thin: int = 1, to_host: bool = True,
+                diagnostics: bool = False, chains: int = None, iterations: int = None, nvars: int = None):
+        """collective (when given a sampler): Trace.predict over the chains of ALL ranks -- one all-gather that stays on the device,
+        evaluated there (rh_predict_device).  sampler_or_gathered: a Sampler, or the device pointer allgather_draws(to_host=False)
+        returned together with chains (world * per rank) / iterations / nvars."""
+        from .sampler import predict_device
+        if isinstance(sampler_or_gathered, int):
+            ptr = sampler_or_gathered
+            count = int(iterations) - int(first) if count is None else int(count)
+        else:
+            s = sampler_or_gathered
+            chains, iterations, nvars = self.world * s.chains, s.iterations, s.model.nVars
+            count = s.progress()[1] - int(first) if count is None else int(count)
+            ptr = self.allgather_draws(s, to_host=False)
+        return predict_device(predictor, ptr, chains, iterations, nvars, device=self.device, first=first, count=count, thin=thin,
+                              to_host=to_host, diagnostics=diagnostics)
+
     def allreduce_max(self, v: float) -> float:
         a = np.array([float(v)])
         _capi.check(_capi.lib().rh_comm_allreduce_max(self._h, _capi.dptr(a)))

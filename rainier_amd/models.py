@@ -182,6 +182,50 @@ def funnel_predict(dim: int = 10):
     return g.compile_requirements([y] + xs), dim
 
 
+def linreg_predict(k: int = 3, x=(0.5, -1.0, 2.0)):
+    """Predictions of cfg 2's regression at a new covariate vector x over linreg()'s parameters (s, a, b_0..b_{k-1}): the
+    regression line a + b.x and the noise scale sigma = exp(s).  (rir, n_requirements) is not returned here -- the rir alone,
+    the form R.Predictor takes; it has 2 requirements."""
+    g = Graph(2 + k, [])
+    mu = g.param(1)
+    for j in range(k):
+        mu = mu + g.param(2 + j) * float(x[j])
+    return g.compile_requirements([mu, g.param(0).exp()])
+
+
+def sparse_predict(nvars: int = 704):
+    """A prediction that reads 4 of `nvars` parameters -- the first, the last and an adjacent pair in the middle: the staging of
+    csrc/device/rh_predict.hip.h that gathers the referenced slots only.  (rir, n_requirements)"""
+    g = Graph(nvars, [])
+    a, b, c, d = g.param(0), g.param(nvars // 2 - 1), g.param(nvars // 2), g.param(nvars - 1)
+    return g.compile_requirements([a + b * c, (d * 0.25).exp() * a, b - c, d]), 4
+
+
+def dense_predict(nvars: int = 704):
+    """A prediction that reads every one of `nvars` parameters: a weighted sum in index order, and its exp-scaled last entry.
+    (rir, n_requirements)"""
+    g = Graph(nvars, [])
+    s = g.param(0) * 1.0
+    for i in range(1, nvars):
+        s = s + g.param(i) * (1.0 / (1 + i % 7))
+    return g.compile_requirements([s, g.param(nvars - 1) * (s * 0.001).exp()]), 2
+
+
+def eight_schools_predict():
+    """The school effects of cfg 3 (bench/stan/EightSchools.scala): theta_j = mu + tau * eta_j with mu = 5 m, tau = |5 c| over
+    eight_schools()'s parameters (m, c, z_1..z_8).  (rir, n_requirements)"""
+    g = Graph(10, [])
+    mu, tau = g.param(0) * 5.0, (g.param(1) * 5.0).abs()
+    return g.compile_requirements([mu + tau * g.param(2 + j) for j in range(8)]), 8
+
+
+def lookup_predict(nvars: int = 4):
+    """A prediction through a Lookup over parameters whose index -- the truncation of 2 * theta_0 -- leaves the table [0, nvars - 1)
+    for some draws (RH_E_LOOKUP).  (rir, n_requirements)"""
+    g = Graph(nvars, [])
+    return g.compile_requirements([g.lookup(g.param(0) * 2.0, [g.param(i) for i in range(1, nvars)], 0)]), 1
+
+
 def nemes_log_gamma(z):
     """Combinatorics.gamma (core/Combinatorics.scala:10-35): log Gamma by Nemes' approximation on z+1 minus log z, with the
     reference's exact special cases gamma(0) = inf, gamma(1) = gamma(2) = 0.  (numpy, for data-only columns.)"""

@@ -205,6 +205,16 @@ class Trace:
         """List of (rHat, effectiveSampleSize) per parameter -- Trace.diagnostics (core/Trace.scala:11-21)."""
         return diagnostics(self.chains)
 
+    def thin(self, n: int) -> "Trace":
+        """Trace.thin(n) (core/Trace.scala:23-32): every chain keeps the iterations with i % n == 0."""
+        if int(n) < 1:
+            raise ValueError("thin: n must be at least 1")
+        return Trace(np.ascontiguousarray(self.chains[:, ::int(n), :]), self.mass, self.stats)
+
+    def predict(self, requirements_rir: bytes, n_requirements: int, device: int = -1, math_mode: int = _capi.MATH_FAST) -> np.ndarray:
+        """Trace.predict (core/Trace.scala:34-41) for a compiled requirements program: [nChains][iterations][n_requirements]."""
+        return predict(requirements_rir, self.chains, n_requirements, device=device, math_mode=math_mode)
+
 
 def diagnostics(chains: np.ndarray):
     ch = np.ascontiguousarray(chains, dtype=np.float64)
@@ -244,6 +254,56 @@ def predict(requirements_rir: bytes, draws: np.ndarray, n_requirements: int, dev
     opts = _capi.compile_opts(device, math_mode)
     _capi.check(_capi.lib().rh_requirements_eval(blob, len(requirements_rir), C.byref(opts), _capi.dptr(flat), flat.shape[0], _capi.dptr(out)))
     return out.reshape(d.shape[:-1] + (n_requirements,))
+
+
+class Predictor:
+    """rh_predict: a requirements program (Generator.prepare's compiled part, core/Generator.scala:59-94) compiled once for one
+    device, for Trace.predict over draws that stay there: Sampler.predict, predict_device, Comm.predict."""
+
+    def __init__(self, requirements_rir: bytes, device: int = -1, math_mode: int = _capi.MATH_FAST, fp_contract: bool = False):
+        self._h = C.c_void_p()
+        blob = C.create_string_buffer(requirements_rir, len(requirements_rir))
+        opts = _capi.compile_opts(device, math_mode, fp_contract)
+        _capi.check(_capi.lib().rh_predict_create(blob, len(requirements_rir), C.byref(opts), C.byref(self._h)))
+        self.nreq = _capi.lib().rh_predict_nreq(self._h)
+        self.nvars = _capi.lib().rh_predict_nvars(self._h)
+
+    def close(self):
+        if self._h:
+            _capi.lib().rh_predict_destroy(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+
+
+def _kept(count: int, thin: int) -> int:
+    return max(0, -(-int(count) // max(1, int(thin))))
+
+
+def _predict_result(call, predictor, chains, count, thin, device, to_host, diagnostics, model=None):
+    """shared by Sampler.predict and predict_device: call(host_out or None, byref(dev_out)) -> rc"""
+    kept = _kept(count, thin)
+    out = np.zeros((chains, kept, predictor.nreq)) if to_host else None
+    ptr = C.c_void_p()
+    _capi.check(call(_capi.dptr(out) if to_host else None, C.byref(ptr)), model)
+    values = out if to_host else ptr.value
+    if not diagnostics:
+        return values
+    # the handle's output buffer has rh_diagnostics_device's layout [chains][kept][nreq]: analysed where it is, no copy
+    diag, mean, var = diagnostics_device(ptr.value, chains, kept, predictor.nreq, device=device, moments=True)
+    return values, diag, mean, var
+
+
+def predict_device(predictor: Predictor, ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0,
+                   count: Optional[int] = None, thin: int = 1, to_host: bool = True, diagnostics: bool = False):
+    """Trace.predict (with Trace.thin applied to the window) over a device buffer [chains][iterations][nvars]: the kept iterations
+    are first + j * thin.  Returns [chains][kept][nreq] (to_host = False: the device pointer of the predictor's own buffer, valid
+    until its next call); with diagnostics = True (values, diag, mean, var) of the predictions."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda host, dev: _capi.lib().rh_predict_device(predictor._h, C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars),
+                                                           int(first), count, int(thin), host, dev)
+    return _predict_result(call, predictor, int(chains), count, thin, int(device), to_host, diagnostics)
 
 
 class Sampler:
@@ -303,6 +363,16 @@ class Sampler:
         _capi.check(_capi.lib().rh_sampler_diagnostics(self._h, int(first), count, _capi.dptr(rhat), _capi.dptr(ess), _capi.dptr(mean),
                                                        _capi.dptr(var)), self.model._h)
         return _diag_result(rhat, ess, mean, var, moments)
+
+    def predict(self, predictor: Predictor, first: int = 0, count: Optional[int] = None, thin: int = 1, to_host: bool = True,
+                diagnostics: bool = False):
+        """Trace.predict over the draws where they are (rh_sampler_predict), with Trace.thin applied to the window: the kept
+        iterations are first + j * thin; count = None: everything completed so far.  Returns [chains][kept][nreq] (to_host = False:
+        the device pointer of the predictor's buffer); with diagnostics = True (values, diag, mean, var) of the predictions."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda host, dev: _capi.lib().rh_sampler_predict(self._h, predictor._h, int(first), count, int(thin), host, dev)
+        # (device -1: the current one, which rh_sampler_predict has just made the sampler's)
+        return _predict_result(call, predictor, self.chains, count, thin, -1, to_host, diagnostics, self.model._h)
 
     def mass_dense(self) -> np.ndarray:
         """DenseMassMatrix.elements of every chain: [chains][nVars][nVars] (DenseMassMatrixTuner only)."""
