@@ -327,6 +327,33 @@ int rh_sampler_predict(rh_sampler *s, rh_predict *p, int32_t first, int32_t coun
 int rh_predict_device(rh_predict *p, const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars,
                       int32_t first, int32_t count, int32_t thin, double *host_out, void **dev_out);
 
+/* ---- posterior summaries over device-resident draws: precis / hdpi (rainier-notebook package.scala:327-342, 367-418, 456-469) ----
+ * The pooled column of parameter p: x[c][first + j*thin][p], chain-major, j = 0 .. kept-1, kept = ceil(count/thin) (the window
+ * and thinning rule of rh_sampler_predict); N = chains * kept.  Every figure reads the column SORTED in java.lang.Double.compare's
+ * order (-0.0 before +0.0; every NaN, read as the positive quiet NaN, after +inf); it is sorted on the device
+ * (csrc/device/rh_summary.hip.h) and never leaves it.
+ *   quantiles[p][k] = sorted[min(N-1, (int64)floor((double)N * probs[k]))], 0 <= probs[k] <= 1, 1 <= nprobs <= 16
+ *                     (precis: data(math.floor(data.size * 0.055).toInt)); the indices are computed on the host, in double.
+ *   hdpi[p]         = for 0 < hdpi_prob <= 1 and idx = (int64)ceil(hdpi_prob * N): (sorted[0], sorted[N-1]) if idx == N, else the
+ *                     pair (sorted[i], sorted[i+idx]) of the smallest width over i in [0, N-idx); widths compare in
+ *                     Double.compare's order and the smallest i wins a tie (minBy's first minimum).  A column that holds a NaN
+ *                     gives (NaN, NaN): the reference's answer there depends on its comparison order.  hdpi_prob <= 0: not asked
+ *                     for, hdpi is not written.
+ *   mean[p], sd[p]  = sum x / N and sqrt(sum (x - mean)^2 / N), the population form (computeParamStats), in two passes.
+ * Sums run in a fixed order that depends on N alone: the same window gives the same bits on every call.  mean / sd [nvars],
+ * quantiles [nvars][nprobs], hdpi [nvars][2]; each may be NULL.  The sort workspace is capped at 128 MiB (the parameters are
+ * walked in chunks); a single column beyond it (2 * N * 8 bytes) returns RH_E_UNSUPPORTED.  A broken window, nprobs outside
+ * 1 .. 16, a probability outside [0, 1] or hdpi_prob > 1: RH_E_INVALID.  No device: RH_E_DEVICE (no CPU fallback).
+ * The sampler form goes to the sampler's stream behind its pending work, is not part of rh_timing and does not alter the chains;
+ * count <= iterations completed - first. */
+int rh_sampler_summary(rh_sampler *s, int32_t first, int32_t count, int32_t thin, const double *probs, int32_t nprobs,
+                       double hdpi_prob, double *mean, double *sd, double *quantiles, double *hdpi);
+/* the same over any device buffer [chains][iterations][nvars] on `device` (-1: the current one), e.g. a predictor's *dev_out or
+ * rh_comm_allgather_draws' *dev_out; synchronises the device before and after */
+int rh_summary_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                      int32_t count, int32_t thin, const double *probs, int32_t nprobs, double hdpi_prob, double *mean, double *sd,
+                      double *quantiles, double *hdpi);
+
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */
 int rh_device_count(void);

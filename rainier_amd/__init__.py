@@ -7,5 +7,6 @@
 """
 from .sampler import (DefaultConfig, DenseMassMatrixTuner, DensityFunction, DiagonalMassMatrix, DiagonalMassMatrixTuner,  # noqa: F401
                       DualAvgTuner, EHMC, EHMCSampler, HMC, HMCSampler, IdentityMassMatrixTuner, Model, NUTSSampler, Predictor,
-                      RainierHipError, Sampler, SamplerConfig, StaticMassMatrix, StaticStepSize, Trace,
-                      diagnostics, diagnostics_device, make_config, predict, predict_device, sample_multi)
+                      RainierHipError, Sampler, SamplerConfig, StaticMassMatrix, StaticStepSize, Summary, Trace,
+                      diagnostics, diagnostics_device, format_precis, make_config, predict, predict_device, sample_multi,
+                      summary_device)

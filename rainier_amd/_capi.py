@@ -32,6 +32,8 @@ EXPORTS = [
     "rh_comm_unique_id", "rh_comm_create", "rh_comm_destroy", "rh_comm_allgather_draws", "rh_comm_allreduce_max", "rh_device_synchronize",
     # Trace.predict / Trace.thin over device-resident draws (core/Trace.scala:23-41, core/Generator.scala:59-94)
     "rh_predict_create", "rh_predict_destroy", "rh_predict_nreq", "rh_predict_nvars", "rh_sampler_predict", "rh_predict_device",
+    # precis / hdpi over device-resident draws (rainier-notebook package.scala:327-342, 367-418)
+    "rh_sampler_summary", "rh_summary_device",
 ]
 
 
@@ -121,6 +123,10 @@ def lib():
     L.rh_sampler_predict.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(vp)]
     L.rh_predict_device.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(vp)]
     L.rh_lower_predict.argtypes = [vp, C.c_size_t, C.POINTER(CompileOpts), C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(vp)]
+    L.rh_sampler_summary.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32, C.c_double, dp, dp, dp, dp]
+    L.rh_summary_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32, C.c_double,
+                                    dp, dp, dp, dp]
+    L.rh_summary_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_comm_unique_id.argtypes = [C.c_char_p]
     L.rh_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.rh_comm_destroy.argtypes = [vp]
@@ -257,6 +263,18 @@ def trace_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_trace_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def summary_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_summary.hip.h (precis / hdpi on the device: the segmented sort and what reads it) -> code object for `arch`,
+    without a device: compiled through the kernel cache and judged as before a launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_summary_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

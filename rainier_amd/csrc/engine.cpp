@@ -49,6 +49,9 @@ static const char *kTraceSrc =   // Trace.diagnostics on the device: model-indep
 static const char *kPredictSrc =   // Trace.predict on the device: follows the generated rh_pred_eval of one requirements program
 #include "gen/rh_predict.inc"
     ;
+static const char *kSummarySrc =   // precis / hdpi on the device: model-independent, a code object of its own
+#include "gen/rh_summary.inc"
+    ;
 namespace {
 thread_local std::string g_err;
 std::atomic<long> g_compiles{0};   // hiprtc compilations of this process (cache misses): rh_compile_count
@@ -408,7 +411,7 @@ std::string cache_path(const std::string &arch, const std::string &source, const
   std::snprintf(name, sizeof name, "/%016llx", (unsigned long long)h);
   return cache_dir() + name;
 }
-// suffix: ".hsaco" for a model's code object; the model-independent ones (rh_trace.hip.h) are kept apart under a name of their own,
+// suffix: ".hsaco" for a model's code object; the model-independent ones (rh_trace.hip.h, rh_summary.hip.h) are kept apart under a name of their own,
 // so that what sweeps the cache's *.hsaco files (the census of GENERATED control flow, tools/unproven_census.py) sees models only
 std::vector<char> build_source(const std::string &arch, const std::string &source, const std::string &extra = std::string(),
                                const char *suffix = ".hsaco") {
@@ -2647,5 +2650,150 @@ extern "C" int rh_lower_predict(const void *rir, size_t rir_len, const rh_compil
     predict_lower(rir, rir_len, opts, arch && *arch ? arch : "gfx950", L, code_size != nullptr);
     if (code_size) *code_size = L.code.size();
     if (code_out && code_size) { *code_out = std::malloc(L.code.size()); std::memcpy(*code_out, L.code.data(), L.code.size()); }
+  });
+}
+
+// ---- precis / hdpi over device-resident draws (device/rh_summary.hip.h) -------------------------------------------------------------
+// The reference sorts the pooled column of every parameter on the host (rainier-notebook package.scala:327-342, 367-418); here the
+// columns are sorted where the draws are -- tile sorts, merge passes between two workspace buffers, one finish workgroup per
+// parameter -- and only the figures come back.  One code object per architecture, cached and judged like the trace kernels'.
+namespace {
+const int kSumBlock = 256, kSumTile = 4096, kSumMergeTile = 2048, kSumMaxProbs = 16;   // RS_BLOCK, RS_TILE, RS_MERGE_TILE, RS_MAX_PROBS
+const long long kSumWsCap = 128ll << 20;                                               // RS_WS_CAP_BYTES
+struct SummaryKernels { hipModule_t module = nullptr; hipFunction_t k_sort = nullptr, k_merge = nullptr, k_finish = nullptr; };
+std::mutex g_summary_mu;
+std::map<int, SummaryKernels> g_summary;   // by device ordinal, kept for the process
+
+std::vector<char> summary_code(const std::string &arch) {
+  const std::vector<char> code = build_source(arch, std::string("// generated by rainier-hip: posterior summaries\n") + kSummarySrc, std::string(), ".summary.co");
+  for (const char *k : {"rh_summary_sort_kernel", "rh_summary_merge_kernel", "rh_summary_finish_kernel"}) {
+    std::string why;
+    if (kernel_health(code, k, &why) != KH_OK) throw Fail{RH_E_UNSUPPORTED, "the summary kernels are not fit to run on this toolchain: " + (why.empty() ? std::string(k) + " is missing" : why)};
+    rh::KernelMeta km;
+    if (!rh::kernel_meta(code, k, km) || km.vgpr_spills != 0 || km.sgpr_spills != 0 || km.scratch_bytes != 0 || rh::kernel_touches_scratch(code, k) != 0)
+      throw Fail{RH_E_UNSUPPORTED, std::string(k) + ": spilled registers or scratch memory"};
+  }
+  return code;
+}
+const SummaryKernels &summary_kernels(int dev) {
+  std::lock_guard<std::mutex> lk(g_summary_mu);
+  SummaryKernels &t = g_summary[dev];
+  if (t.k_sort) return t;
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, dev));
+  std::string arch = prop.gcnArchName;
+  if (arch.find(':') != std::string::npos) arch = arch.substr(0, arch.find(':'));
+  const std::vector<char> code = summary_code(arch);
+  HIPCHK(hipModuleLoadData(&t.module, code.data()));
+  HIPCHK(hipModuleGetFunction(&t.k_merge, t.module, "rh_summary_merge_kernel"));
+  HIPCHK(hipModuleGetFunction(&t.k_finish, t.module, "rh_summary_finish_kernel"));
+  HIPCHK(hipModuleGetFunction(&t.k_sort, t.module, "rh_summary_sort_kernel"));
+  return t;
+}
+
+// the argument rules shared by the two entry points (before any device call, so that they hold on a machine without one)
+int summary_check_args(const char *fn, const void *draws, int64_t chains, int64_t iterations, int64_t nvars, int32_t first, int32_t count,
+                       int32_t thin, const double *probs, int32_t nprobs, double hdpi_prob) {
+  const std::string f(fn);
+  if (!draws || !probs) { g_err = f + ": NULL argument"; return RH_E_INVALID; }
+  if (chains < 1 || nvars < 1 || iterations < 0 || first < 0 || count < 1 || thin < 1 || (int64_t)first + count > iterations) {
+    g_err = f + ": the window [first, first + count) must hold at least 1 of the completed iterations, thin >= 1";
+    return RH_E_INVALID;
+  }
+  if (nprobs < 1 || nprobs > kSumMaxProbs) { g_err = f + ": nprobs must be in 1 .. 16"; return RH_E_INVALID; }
+  for (int k = 0; k < nprobs; k++)
+    if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) { g_err = f + ": every probability must be in [0, 1]"; return RH_E_INVALID; }
+  if (!(hdpi_prob <= 1.0)) { g_err = f + ": hdpi_prob must be in (0, 1] (<= 0: not asked for)"; return RH_E_INVALID; }
+  return RH_OK;
+}
+
+// draws: device pointer on `dev` (an existing device: the caller's business), [chains][iterations][nvars]; the launches go to `stream`
+// and are waited for
+void summary_run(const void *draws, int dev, hipStream_t stream, int chains, long long iterations, int nvars, int first, int count, int thin,
+                 const double *probs, int nprobs, double hdpi_prob, double *mean, double *sd, double *quantiles, double *hdpi) {
+  long long kept = ((long long)count + thin - 1) / thin, N = (long long)chains * kept;
+  const long long per_param = 2 * N * (long long)sizeof(unsigned long long);   // the two ping-pong buffers
+  if (per_param > kSumWsCap)
+    throw Fail{RH_E_UNSUPPORTED, "summary: one pooled column of " + std::to_string(N) + " values needs " + std::to_string(per_param) +
+                                     " bytes of sort workspace, beyond the cap of " + std::to_string(kSumWsCap) + " (thin the window)"};
+  // the indices, on the host, in double (precis: data(math.floor(data.size * q).toInt); hdpi: math.ceil(prob * sorted.size).toInt)
+  long long idx[kSumMaxProbs] = {0};
+  for (int k = 0; k < nprobs; k++) idx[k] = std::min<long long>(N - 1, (long long)std::floor((double)N * probs[k]));
+  long long hidx = 0;
+  if (hdpi_prob > 0.0) hidx = std::max<long long>(1, std::min<long long>(N, (long long)std::ceil(hdpi_prob * (double)N)));
+  HIPCHK(hipSetDevice(dev));
+  const SummaryKernels &K = summary_kernels(dev);
+  const long long pc = std::max<long long>(1, std::min<long long>(kSumWsCap / per_param, nvars));
+  const size_t nres = (size_t)nvars * (size_t)(4 + nprobs);
+  DevBuf ws((size_t)per_param * (size_t)pc), res(sizeof(double) * nres), didx(sizeof idx);
+  HIPCHK(hipMemcpyAsync(didx.p, idx, sizeof idx, hipMemcpyHostToDevice, stream));
+  double *d_mean = (double *)res.p, *d_sd = d_mean + nvars, *d_hdpi = d_sd + nvars, *d_quant = d_hdpi + 2 * (size_t)nvars;
+  HIPCHK(hipMemsetAsync(res.p, 0, sizeof(double) * nres, stream));
+  const double *d_draws = (const double *)draws;
+  const long long *d_idx = (const long long *)didx.p;
+  const long long tiles = (N + kSumTile - 1) / kSumTile, mtiles = (N + kSumMergeTile - 1) / kSumMergeTile;
+  long long nv = nvars, first64 = first, thin64 = thin;
+  for (long long p0 = 0; p0 < nvars; p0 += pc) {
+    int p_lo = (int)p0, p_cnt = (int)std::min<long long>(pc, nvars - p0);
+    if (tiles * p_cnt > 0x7fffffffll || mtiles * p_cnt > 0x7fffffffll) throw Fail{RH_E_UNSUPPORTED, "summary: too many tiles for one launch"};
+    unsigned long long *src = (unsigned long long *)ws.p, *dst = src + (size_t)pc * (size_t)N;
+    void *a1[] = {&d_draws, &iterations, &nv, &first64, &thin64, &kept, &N, &p_lo, &p_cnt, &src};
+    launch(K.k_sort, (unsigned)(tiles * p_cnt), kSumBlock, stream, a1);
+    for (long long L = kSumTile; L < N; L *= 2) {
+      void *a2[] = {&src, &dst, &N, &L, &p_cnt};
+      launch(K.k_merge, (unsigned)(mtiles * p_cnt), kSumBlock, stream, a2);
+      std::swap(src, dst);
+    }
+    void *a3[] = {&src, &N, &d_idx, &nprobs, &hidx, &p_lo, &d_mean, &d_sd, &d_quant, &d_hdpi};
+    launch(K.k_finish, (unsigned)p_cnt, kSumBlock, stream, a3);
+  }
+  std::vector<double> host(nres);
+  HIPCHK(hipMemcpyAsync(host.data(), res.p, sizeof(double) * nres, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (mean) std::memcpy(mean, host.data(), sizeof(double) * nvars);
+  if (sd) std::memcpy(sd, host.data() + nvars, sizeof(double) * nvars);
+  if (hdpi && hidx > 0) std::memcpy(hdpi, host.data() + 2 * (size_t)nvars, sizeof(double) * 2 * nvars);
+  if (quantiles) std::memcpy(quantiles, host.data() + 4 * (size_t)nvars, sizeof(double) * (size_t)nvars * nprobs);
+}
+}  // namespace
+
+extern "C" int rh_sampler_summary(rh_sampler *s, int32_t first, int32_t count, int32_t thin, const double *probs, int32_t nprobs,
+                                  double hdpi_prob, double *mean, double *sd, double *quantiles, double *hdpi) {
+  if (!s) { g_err = "rh_sampler_summary: NULL"; return RH_E_INVALID; }
+  const int rc0 = summary_check_args("rh_sampler_summary", s->d_draws ? s->d_draws : (const void *)s, s->chains, s->it_done,
+                                     (int64_t)s->m->prog.n_params, first, count, thin, probs, nprobs, hdpi_prob);
+  if (rc0 != RH_OK) { s->m->err = g_err; return rc0; }
+  std::lock_guard<std::mutex> lk(s->m->mu);
+  // on the sampler's own stream, behind whatever it still has in flight; reads the draws only; not part of rh_timing's figures
+  return guard(s->m, [&] {
+    summary_run(s->d_draws, s->m->device, s->m->stream, s->chains, s->cfg.iterations, (int)s->m->prog.n_params, first, count, thin, probs,
+                nprobs, hdpi_prob, mean, sd, quantiles, hdpi);
+  });
+}
+
+extern "C" int rh_summary_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                                 int32_t count, int32_t thin, const double *probs, int32_t nprobs, double hdpi_prob, double *mean,
+                                 double *sd, double *quantiles, double *hdpi) {
+  const int rc0 = summary_check_args("rh_summary_device", dev_draws, chains, iterations, nvars, first, count, thin, probs, nprobs, hdpi_prob);
+  if (rc0 != RH_OK) return rc0;
+  return guard(nullptr, [&] {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Fail{RH_E_DEVICE, "no HIP device available: the engine has no CPU fallback"};
+    if (device < 0) HIPCHK(hipGetDevice(&device));
+    if (device >= ndev) throw Fail{RH_E_INVALID, "rh_summary_device: no such device"};
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());   // whoever filled the buffer (a sampler's stream, a predictor, the RCCL gather) has finished
+    summary_run(dev_draws, device, nullptr, chains, iterations, nvars, first, count, thin, probs, nprobs, hdpi_prob, mean, sd, quantiles, hdpi);
+  });
+}
+
+// No device needed: device/rh_summary.hip.h -> code object for `arch` (through the kernel cache), judged as before a launch.
+// *code_out: the code object (malloc'ed, the caller frees it with rh_free).  build() calls it so that the code object is in the
+// in-tree kernel cache; the CPU tests read the kernels' metadata from it.
+extern "C" int rh_summary_lower_only(const char *arch, void **code_out, size_t *code_size) {
+  return guard(nullptr, [&] {
+    const std::vector<char> code = summary_code(arch && *arch ? arch : "gfx950");
+    if (code_size) *code_size = code.size();
+    if (code_out) { *code_out = std::malloc(code.size()); std::memcpy(*code_out, code.data(), code.size()); }
   });
 }

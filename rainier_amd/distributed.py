@@ -91,6 +91,15 @@ class Comm:
         return predict_device(predictor, ptr, chains, iterations, nvars, device=self.device, first=first, count=count, thin=thin,
                               to_host=to_host, diagnostics=diagnostics)
 
+    def summary(self, sampler, first: int = 0, count=None, thin: int = 1, probs=(0.055, 0.945), hdpi=0.89):
+        """collective: precis' figures and hdpi over the chains of ALL ranks -- one all-gather that stays on the device, sorted and
+        summarised there (rh_summary_device); every rank gets the same Summary as Sampler.summary gives for its own chains"""
+        from .sampler import summary_device
+        count = sampler.progress()[1] - int(first) if count is None else int(count)
+        ptr = self.allgather_draws(sampler, to_host=False)
+        return summary_device(ptr, self.world * sampler.chains, sampler.iterations, sampler.model.nVars, device=self.device,
+                              first=first, count=count, thin=thin, probs=probs, hdpi=hdpi)
+
     def allreduce_max(self, v: float) -> float:
         a = np.array([float(v)])
         _capi.check(_capi.lib().rh_comm_allreduce_max(self._h, _capi.dptr(a)))

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -306,6 +306,53 @@ def predict_device(predictor: Predictor, ptr: int, chains: int, iterations: int,
     return _predict_result(call, predictor, int(chains), count, thin, int(device), to_host, diagnostics)
 
 
+class Summary(NamedTuple):
+    """precis / hdpi of every parameter (rainier-notebook package.scala:327-342, 367-418): mean [nvars], sd [nvars] (population
+    form), quantiles [nvars][nprobs] (the order statistics at floor(N * q)), hdpi [nvars][2] (None when not asked for), and the
+    probabilities they were asked at."""
+    mean: np.ndarray
+    sd: np.ndarray
+    quantiles: np.ndarray
+    hdpi: Optional[np.ndarray]
+    probs: Tuple[float, ...] = (0.055, 0.945)
+    hdpi_prob: Optional[float] = 0.89
+
+
+def _summary_result(call, nvars, probs, hdpi, model=None):
+    """shared by Sampler.summary and summary_device: call(probs, nprobs, hdpi_prob, mean, sd, quantiles, hdpi) -> rc"""
+    pr = np.ascontiguousarray([float(q) for q in probs], dtype=np.float64)
+    mean, sd, quant, hd = np.zeros(nvars), np.zeros(nvars), np.zeros((nvars, len(pr))), np.zeros((nvars, 2))
+    hp = 0.0 if hdpi is None else float(hdpi)
+    _capi.check(call(_capi.dptr(pr), len(pr), hp, _capi.dptr(mean), _capi.dptr(sd), _capi.dptr(quant), _capi.dptr(hd)), model)
+    asked = hp > 0.0
+    return Summary(mean, sd, quant, hd if asked else None, tuple(pr.tolist()), hp if asked else None)
+
+
+def summary_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
+                   thin: int = 1, probs: Sequence[float] = (0.055, 0.945), hdpi: Optional[float] = 0.89) -> Summary:
+    """precis' figures and hdpi over a device buffer [chains][iterations][nvars] (a sampler's draws, a predictor's to_host = False
+    result, Comm.allgather_draws(to_host=False)), computed where the draws are (rh_summary_device): every parameter's pooled column
+    over the kept iterations first + j * thin is sorted on the device.  hdpi = None: no highest-density interval."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_summary_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count,
+                                                    int(thin), *a)
+    return _summary_result(call, int(nvars), probs, hdpi)
+
+
+def format_precis(names: Sequence[str], summary: Summary) -> str:
+    """precis' table (rainier-notebook package.scala:393-417, without the correlations) as a string: Mean, StdDev and the first two
+    order statistics of `summary`, %10.2f, one line per parameter."""
+    names = [str(k) for k in names]
+    if len(names) != len(summary.mean) or summary.quantiles.shape[1] < 2:
+        raise ValueError("format_precis: one name per parameter and at least two probabilities")
+    width = max(len(k) for k in names)
+    heads = ["Mean", "StdDev"] + ["%g%%" % (100.0 * q) for q in summary.probs[:2]]
+    lines = ["".ljust(width) + "".join("%10s" % h for h in heads)]
+    for k, m, s, q in zip(names, summary.mean, summary.sd, summary.quantiles):
+        lines.append(k.ljust(width) + "".join("%10.2f" % v for v in (m, s, q[0], q[1])))
+    return "\n".join(lines)
+
+
 class Sampler:
     """Device-resident chains: split form of Driver.sample used by bench.py (create -> warmup -> run)."""
 
@@ -373,6 +420,15 @@ class Sampler:
         call = lambda host, dev: _capi.lib().rh_sampler_predict(self._h, predictor._h, int(first), count, int(thin), host, dev)
         # (device -1: the current one, which rh_sampler_predict has just made the sampler's)
         return _predict_result(call, predictor, self.chains, count, thin, -1, to_host, diagnostics, self.model._h)
+
+    def summary(self, first: int = 0, count: Optional[int] = None, thin: int = 1, probs: Sequence[float] = (0.055, 0.945),
+                hdpi: Optional[float] = 0.89) -> Summary:
+        """precis' figures and hdpi of the draws where they are (rh_sampler_summary): mean, sd, the order statistics at `probs` and
+        the highest-density interval of every parameter over the kept iterations first + j * thin of all chains pooled;
+        count = None: everything completed so far.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_summary(self._h, int(first), count, int(thin), *a)
+        return _summary_result(call, self.model.nVars, probs, hdpi, self.model._h)
 
     def mass_dense(self) -> np.ndarray:
         """DenseMassMatrix.elements of every chain: [chains][nVars][nVars] (DenseMassMatrixTuner only)."""
