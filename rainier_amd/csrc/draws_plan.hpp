@@ -1,0 +1,69 @@
+// draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
+// workspace, how many tiles and merge passes, which order statistics, which predict kernel.  Arithmetic only: no HIP, no allocation,
+// no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
+#ifndef RH_DRAWS_PLAN_HPP
+#define RH_DRAWS_PLAN_HPP
+
+#include <algorithm>
+#include <cmath>
+
+// the constants are the device headers' own: their block routines compile as plain C++ in host mode
+#define RH_TRACE_HOST 1
+#define RH_SUMMARY_HOST 1
+#include "device/rh_trace.hip.h"
+#include "device/rh_summary.hip.h"
+namespace rh_plan {
+// ---- trace diagnostics (device/rh_trace.hip.h) ----
+// parameters per chunk: the workspace [chunk][chains][RT_SL] stays under the cap; whole tiles where a tile fits
+inline long long trace_chunk(int chains, int nvars) {
+  long long pc = RT_WS_CAP_BYTES / ((long long)chains * RT_SL * (long long)sizeof(double));
+  pc = std::max<long long>(1, std::min<long long>(pc, nvars));
+  if (pc >= RT_TP) pc -= pc % RT_TP;
+  return pc;
+}
+inline long long trace_tiles(long long p_cnt) { return (p_cnt + RT_TP - 1) / RT_TP; }
+// ---- posterior summaries (device/rh_summary.hip.h) ----
+struct Summary {
+  long long kept, N;             // kept iterations per chain; values of one pooled column
+  long long per_param, pc;       // workspace bytes of one parameter (the two ping-pong buffers of keys); parameters per chunk
+  bool over_cap;                 // one column alone is beyond RS_WS_CAP_BYTES
+  long long tiles, mtiles;       // tile sorts and merge workgroups per parameter
+  int passes;                    // merge passes; pass k merges runs of run(k) keys
+  long long idx[RS_MAX_PROBS];   // order statistics (precis: data(math.floor(data.size * q).toInt))
+  long long hidx;                // hdpi's span (math.ceil(prob * sorted.size).toInt, in 1 .. N); 0: not asked for
+  long long run(int k) const { return (long long)RS_TILE << k; }
+};
+inline Summary summary_plan(long long chains, long long count, long long thin, long long nvars, const double *probs, int nprobs, double hdpi_prob) {
+  Summary P = {};
+  P.kept = (count + thin - 1) / thin;
+  P.N = chains * P.kept;
+  P.per_param = 2 * P.N * (long long)sizeof(unsigned long long);
+  P.over_cap = P.per_param > RS_WS_CAP_BYTES;
+  P.pc = std::max<long long>(1, std::min<long long>(RS_WS_CAP_BYTES / P.per_param, nvars));
+  P.tiles = (P.N + RS_TILE - 1) / RS_TILE;
+  P.mtiles = (P.N + RS_MERGE_TILE - 1) / RS_MERGE_TILE;
+  while (P.run(P.passes) < P.N) P.passes++;
+  for (int k = 0; k < nprobs; k++) P.idx[k] = std::min<long long>(P.N - 1, (long long)std::floor((double)P.N * probs[k]));
+  if (hdpi_prob > 0.0) P.hidx = std::max<long long>(1, std::min<long long>(P.N, (long long)std::ceil(hdpi_prob * (double)P.N)));
+  return P;
+}
+// ---- predict (device/rh_predict.hip.h) ----
+// that header cannot be included without a generated program around it, so these four are mirrors: RP_WAVE, RP_MAX_TILE, RP_LDS_DOUBLES, RP_TILE_FOR
+const int kPredWave = 64, kPredMaxTile = 256, kPredLdsDoubles = 8064;
+inline int pred_tile_for(int stride) {
+  const int rows = kPredLdsDoubles / stride;
+  return rows >= kPredMaxTile ? kPredMaxTile : rows / kPredWave * kPredWave;
+}
+enum { PRED_FLAT = 0, PRED_GATHER = 1, PRED_DIRECT = 2 };   // RP_FLAT, RP_GATHER, RP_DIRECT
+// which kernels a program's source holds (RP_HAVE_FLAT, RP_HAVE_GATHER; the direct kernel stands in for a missing gather kernel)
+inline bool pred_has_flat(int nvars, int nref) { return pred_tile_for(nvars | 1) >= kPredWave && 2 * nref >= nvars; }
+inline bool pred_has_gather(int nref) { return pred_tile_for(nref | 1) >= kPredWave; }
+struct PredictLaunch { int form, tile; };
+// flat when the program has that kernel and thin == 1, else gathered, else direct; the tile is the workgroup's size
+inline PredictLaunch predict_launch(int nvars, int nref, int thin) {
+  if (thin == 1 && pred_has_flat(nvars, nref)) return {PRED_FLAT, pred_tile_for(nvars | 1)};
+  if (pred_has_gather(nref)) return {PRED_GATHER, pred_tile_for(nref | 1)};
+  return {PRED_DIRECT, kPredWave};
+}
+}  // namespace rh_plan
+#endif

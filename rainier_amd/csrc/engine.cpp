@@ -32,48 +32,21 @@
 #include "device/rh_shared.h"
 #include "rir.hpp"
 #include "optimize.hpp"
+#include "engine_internal.hpp"
 
 // device sources embedded at build time (see Makefile: device_src.inc)
-static const char *kSharedSrc =
+const char *const kSharedSrc =
 #include "gen/rh_shared.inc"
     ;
-static const char *kPreludeSrc =
+const char *const kPreludeSrc =
 #include "gen/rh_prelude.inc"
     ;
 static const char *kEngineSrc =
 #include "gen/rh_engine.inc"
     ;
-static const char *kTraceSrc =   // Trace.diagnostics on the device: model-independent, a code object of its own
-#include "gen/rh_trace.inc"
-    ;
-static const char *kPredictSrc =   // Trace.predict on the device: follows the generated rh_pred_eval of one requirements program
-#include "gen/rh_predict.inc"
-    ;
-static const char *kSummarySrc =   // precis / hdpi on the device: model-independent, a code object of its own
-#include "gen/rh_summary.inc"
-    ;
 namespace {
 thread_local std::string g_err;
 std::atomic<long> g_compiles{0};   // hiprtc compilations of this process (cache misses): rh_compile_count
-
-struct Fail {
-  int code;
-  std::string msg;
-};
-#define HIPCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) throw Fail{RH_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-// device allocation released on scope exit (also when a HIP call throws)
-struct DevBuf {
-  void *p = nullptr;
-  explicit DevBuf(size_t bytes) { hipError_t e = hipMalloc(&p, bytes ? bytes : 8); if (e != hipSuccess) throw Fail{RH_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)}; }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-};
 
 uint64_t fnv1a(const std::string &s, uint64_t h = 1469598103934665603ULL) {
   for (unsigned char ch : s) { h ^= ch; h *= 1099511628211ULL; }
@@ -144,6 +117,7 @@ std::vector<char> compile_hip(const std::string &src, const std::string &arch, c
   return code;
 }
 }  // namespace
+std::string &thread_err() { return g_err; }
 
 struct KSet {  // the per-chain sampler kernels of one compiled variant (with / without NUTS support)
   hipModule_t module = nullptr;
@@ -245,6 +219,14 @@ struct rh_sampler {
   std::vector<rh_chain_stats_dev> last_stats;
   int64_t grads_at_reset = 0;
 };
+int guard(rh_model *m, const std::function<void()> &fn) {
+  try { fn(); return RH_OK; }
+  catch (const Fail &f) { g_err = f.msg; if (m) m->err = f.msg; return f.code; }
+  catch (const std::exception &e) { g_err = e.what(); if (m) m->err = e.what(); return RH_E_INVALID; }
+}
+DrawsView sampler_draws(rh_sampler *s) {
+  return {s->d_draws, s->m->device, s->m->stream, s->chains, s->it_done, (int)s->m->prog.n_params, s->cfg.iterations, &s->m->mu, &s->m->err, s->m};
+}
 
 namespace {
 
@@ -413,8 +395,8 @@ std::string cache_path(const std::string &arch, const std::string &source, const
 }
 // suffix: ".hsaco" for a model's code object; the model-independent ones (rh_trace.hip.h, rh_summary.hip.h) are kept apart under a name of their own,
 // so that what sweeps the cache's *.hsaco files (the census of GENERATED control flow, tools/unproven_census.py) sees models only
-std::vector<char> build_source(const std::string &arch, const std::string &source, const std::string &extra = std::string(),
-                               const char *suffix = ".hsaco") {
+}  // namespace
+std::vector<char> build_source(const std::string &arch, const std::string &source, const std::string &extra, const char *suffix) {
   const std::string path = cache_path(arch, source, extra) + suffix;
   std::vector<char> code;
   if (!std::getenv("RH_NO_KERNEL_CACHE") && read_file(path, code)) return code;
@@ -424,6 +406,7 @@ std::vector<char> build_source(const std::string &arch, const std::string &sourc
   if (!std::getenv("RH_NO_KERNEL_CACHE")) write_file(path, code);
   return code;
 }
+namespace {
 // An attempt the engine abandons (build_code lowers the model again with a lighter shape) is not kept as a code object: a small
 // marker with the kernels that were unfit takes its place, so that the next process takes the same decision without compiling.
 // (a marker records a verdict of kernel_health: it carries the version of those rules and whether they were switched off, and a marker
@@ -458,8 +441,8 @@ const char *kNutsDefine = "#define RH_WITH_NUTS 1\n";
 // that fails is replaced by a lighter build of itself (row unroll, chains per wavefront, wavefronts per SIMD) or by another engine;
 // when nothing is left the call fails with RH_E_UNSUPPORTED -- it is never run.  RH_ALLOW_UNHEALTHY=1 (diagnostics: reproducing the
 // fault on a GPU) switches the rule off.
-enum { KH_ABSENT = 0, KH_OK = 1, KH_BAD = 2 };
-int kernel_health(const std::vector<char> &code, const std::string &name, std::string *why = nullptr) {
+}  // namespace
+int kernel_health(const std::vector<char> &code, const std::string &name, std::string *why) {
   rh::KernelMeta km;
   std::vector<std::string> names;
   if (!rh::list_kernels(code, names)) { if (why) *why = name + ": the code object cannot be read"; return KH_BAD; }
@@ -482,6 +465,7 @@ int kernel_health(const std::vector<char> &code, const std::string &name, std::s
   }
   return KH_OK;
 }
+namespace {
 
 // Lower, compile, look at what the compiler did, and lower again with a lighter shape while a kernel the model would launch is
 // not fit to run (every attempt is cached under its own key, so this costs a parse after the first time; the attempts are counted
@@ -746,11 +730,6 @@ KSet &load_variant(rh_model *m, int v) {
   return ks;
 }
 
-int guard(rh_model *m, const std::function<void()> &fn) {
-  try { fn(); return RH_OK; }
-  catch (const Fail &f) { g_err = f.msg; if (m) m->err = f.msg; return f.code; }
-  catch (const std::exception &e) { g_err = e.what(); if (m) m->err = e.what(); return RH_E_INVALID; }
-}
 
 // rh_compile_opts -> emitter options, validated once for rh_model_create and rh_lower_only; returns the device ordinal
 int apply_compile_opts(rh_model *m, const rh_compile_opts *opts) {
@@ -935,10 +914,6 @@ void canonicalize_once(rh_model *m, const double *const *columns, const int64_t 
   nrows_t = nr;
 }
 
-void launch(hipFunction_t f, unsigned grid, unsigned block, hipStream_t s, void **args) {
-  HIPCHK(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, 0, s, args, nullptr));
-}
-
 // ---- create-time self-checks (see selfcheck_engine) ----------------------------------------------------------------------------
 bool selfcheck_enabled() {
   const char *e = rh::unsafe_knob("RH_SELFCHECK");
@@ -1044,11 +1019,7 @@ extern "C" int rh_model_create(const void *rir, size_t rir_len, const double *co
     if (dev < 0) HIPCHK(hipGetDevice(&dev));
     if (dev >= ndev) throw Fail{RH_E_INVALID, "device ordinal out of range"};
     m->device = dev;
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
-    m->arch = prop.gcnArchName;
-    const auto colon = m->arch.find(':');
-    if (colon != std::string::npos) m->arch = m->arch.substr(0, colon);
+    m->arch = device_arch(dev);
     build_code(m);
     load_module(m);
     upload_kpool(m);
@@ -1165,11 +1136,7 @@ extern "C" int rh_model_clone(const rh_model *src, int32_t device, rh_model **ou
     m->n_row_targets_hint = src->n_row_targets_hint; m->rows_unroll_auto = src->rows_unroll_auto; m->unroll_auto = src->unroll_auto;
     m->shape_guessed = src->shape_guessed; m->synth_cols = src->synth_cols; m->ncols_max = src->ncols_max; m->glm_ncols = src->glm_ncols;
     m->device = dev;
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
-    m->arch = prop.gcnArchName;
-    const auto colon = m->arch.find(':');
-    if (colon != std::string::npos) m->arch = m->arch.substr(0, colon);
+    m->arch = device_arch(dev);
     if (m->arch == src->arch) m->code = src->code; else build_code(m);   // (a mixed node: compiled or fetched from the cache for that architecture)
     load_module(m);
     if (m->want_nuts) (void)load_variant(m, 1);
@@ -2233,567 +2200,4 @@ extern "C" int rh_sample_multi(rh_model *const *models, int32_t n_models, const 
   for (int g = 0; g < G; g++)
     if (rcs[(size_t)g] != RH_OK) { g_err = "shard " + std::to_string(g) + ": " + errs[(size_t)g]; return rcs[(size_t)g]; }
   return RH_OK;
-}
-
-// ---- Generator.prepare / Trace.predict: requirements evaluated for every draw on the device ---------------------------
-static const char *kReqKernel = R"RHSRC(
-// one thread per draw: th = draws[d][:], out[d][:] = the requirements (core/Generator.scala:76-84 per draw, batched)
-extern "C" __global__ void __launch_bounds__(256)
-rh_req_kernel(const double *__restrict__ draws, double *__restrict__ out, const long long ndraws, int *__restrict__ err_out) {
-  const long long d = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (d >= ndraws) return;
-  double th[RH_NVARS];
-#pragma unroll
-  for (int i = 0; i < RH_NVARS; i++) th[i] = draws[d * RH_NVARS + i];
-  double o[RH_NREQ];
-  int err = 0;
-  rh_req_eval(th, o, err);
-#pragma unroll
-  for (int m = 0; m < RH_NREQ; m++) out[d * RH_NREQ + m] = o[m];
-  if (err) atomicOr(err_out, 1);
-}
-)RHSRC";
-
-extern "C" int rh_requirements_eval(const void *rir, size_t rir_len, const rh_compile_opts *opts, const double *draws,
-                                    int64_t ndraws, double *out) {
-  if (!draws || !out || ndraws < 0) { g_err = "rh_requirements_eval: bad arguments"; return RH_E_INVALID; }
-  int lookup_err = 0;
-  const int rc = guard(nullptr, [&] {
-    rh::Program P; std::string err;
-    if (!rh::parse_rir(rir, rir_len, P, err)) throw Fail{RH_E_INVALID, err};
-    if (P.kind != 1) throw Fail{RH_E_INVALID, "not a requirements program (header kind != 1)"};
-    rh::EmitOptions eo;
-    int dev = -1;
-    if (opts) { eo.strict_math = opts->math_mode == RH_MATH_STRICT; eo.fp_contract = opts->fp_contract != 0; dev = opts->device; }
-    std::string defines, body;
-    if (!rh::emit_requirements(P, eo, defines, body, err)) throw Fail{RH_E_UNSUPPORTED, err};
-    const std::string src = "// generated by rainier-hip: requirements program\n" + defines + kSharedSrc + "\n" + kPreludeSrc + "\n" + body + kReqKernel;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-      if (rh::knob("RH_LOWER_ONLY")) { (void)build_source("gfx950", src); return; }   // build()/CPU tests: cross-compile only
-      throw Fail{RH_E_DEVICE, "no HIP device available: the engine has no CPU fallback"};
-    }
-    if (dev < 0) HIPCHK(hipGetDevice(&dev));
-    HIPCHK(hipSetDevice(dev));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
-    std::string arch = prop.gcnArchName;
-    if (arch.find(':') != std::string::npos) arch = arch.substr(0, arch.find(':'));
-    const std::vector<char> code = build_source(arch, src);
-    hipModule_t mod; hipFunction_t fn;
-    HIPCHK(hipModuleLoadData(&mod, code.data()));
-    struct Unload { hipModule_t m; ~Unload() { (void)hipModuleUnload(m); } } unload{mod};
-    HIPCHK(hipModuleGetFunction(&fn, mod, "rh_req_kernel"));
-    if (ndraws == 0) return;
-    const size_t nv = P.n_params, nr = P.targets.size();
-    DevBuf bd(sizeof(double) * nv * ndraws), bo(sizeof(double) * nr * ndraws), be(sizeof(int));
-    HIPCHK(hipMemcpy(bd.p, draws, sizeof(double) * nv * ndraws, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(be.p, 0, sizeof(int)));
-    void *dd = bd.p, *dout = bo.p, *de = be.p; long long nd = ndraws;
-    void *args[] = {&dd, &dout, &nd, &de};
-    launch(fn, (unsigned)((ndraws + 255) / 256), 256, nullptr, args);
-    HIPCHK(hipMemcpy(out, bo.p, sizeof(double) * nr * ndraws, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&lookup_err, be.p, sizeof(int), hipMemcpyDeviceToHost));
-  });
-  if (rc == RH_OK && lookup_err) { g_err = "Lookup index out of range during evaluation"; return RH_E_LOOKUP; }
-  return rc;
-}
-
-// ---- Trace.diagnostics (core/Trace.scala:52-120), host side -------------------------------------------
-extern "C" int rh_diagnostics(const double *draws, int32_t chains, int32_t iterations, int32_t nvars, double *rhat, double *ess) {
-  if (!draws || !rhat || !ess || iterations < 2 || nvars < 1) { g_err = "rh_diagnostics: bad arguments"; return RH_E_INVALID; }
-  if (chains < 2) { g_err = "requirement failed: diagnostics requires multiple chains"; return RH_E_INVALID; }  // Trace.scala:12
-  const double m = chains, n = iterations;
-  std::vector<double> tr((size_t)chains * iterations), means(chains);
-  for (int p = 0; p < nvars; p++) {
-    for (int c = 0; c < chains; c++)
-      for (int i = 0; i < iterations; i++) tr[(size_t)c * iterations + i] = draws[((size_t)c * iterations + i) * nvars + p];
-    for (int c = 0; c < chains; c++) { double s = 0; for (int i = 0; i < iterations; i++) s += tr[(size_t)c * iterations + i]; means[c] = s / n; }
-    double mm = 0; for (double x : means) mm += x; mm /= m;
-    double bs = 0; for (double x : means) bs += (x - mm) * (x - mm);
-    const double b = (n / (m - 1)) * bs;
-    double ws = 0;
-    for (int c = 0; c < chains; c++) { double s = 0; for (int i = 0; i < iterations; i++) { const double d = tr[(size_t)c * iterations + i] - means[c]; s += d * d; } ws += s / (n - 1); }
-    const double w = ws / m, v = (n - 1) / n * w + b / n;
-    rhat[p] = std::sqrt(v / w);
-    double acc = 0; int lag = 1;
-    for (;;) {
-      double vt = 0;
-      for (int c = 0; c < chains; c++) {
-        const double *t = &tr[(size_t)c * iterations]; double s = 0;
-        for (int i = lag; i < iterations; i++) { const double d = t[i] - t[i - lag]; s += d * d; }
-        vt += s / (double)(iterations - lag);
-      }
-      vt /= m;
-      const double pt = 1.0 - (vt / (2.0 * v));
-      if (pt > 0.0 && lag < 100) { acc += pt; lag += 1; } else break;  // lag == n gives 0/0 = NaN and stops, as in the reference
-    }
-    ess[p] = n * m / (1 + (2 * acc));
-  }
-  return RH_OK;
-}
-
-// ---- Trace.diagnostics over device-resident draws (device/rh_trace.hip.h) ------------------------------------------------
-// The host form above needs the draws on the host and one thread; this one leaves them where the sampler (or the RCCL gather) put
-// them.  One code object per architecture, cached on disk like a model's, inspected by kernel_health before its first launch.
-namespace {
-const int kTraceTile = 16, kTraceSlots = 101, kTraceBlock = 256, kTraceFinBlock = 128;   // RT_TP, RT_SL, RT_BLOCK, RT_FIN_BLOCK
-const long long kTraceWsCap = 128ll << 20;                                               // RT_WS_CAP_BYTES
-struct TraceKernels { hipModule_t module = nullptr; hipFunction_t k_chain = nullptr, k_finish = nullptr; };
-std::mutex g_trace_mu;
-std::map<int, TraceKernels> g_trace;   // by device ordinal (a module belongs to its device's context; kept for the process)
-
-std::vector<char> trace_code(const std::string &arch) {
-  const std::vector<char> code = build_source(arch, std::string("// generated by rainier-hip: trace diagnostics\n") + kTraceSrc, std::string(), ".trace.co");
-  for (const char *k : {"rh_trace_chain_kernel", "rh_trace_finish_kernel"}) {
-    std::string why;
-    if (kernel_health(code, k, &why) != KH_OK) throw Fail{RH_E_UNSUPPORTED, "the trace kernels are not fit to run on this toolchain: " + (why.empty() ? std::string(k) + " is missing" : why)};
-    rh::KernelMeta km;
-    if (!rh::kernel_meta(code, k, km) || km.vgpr_spills != 0 || km.scratch_bytes != 0 || rh::kernel_touches_scratch(code, k) != 0)
-      throw Fail{RH_E_UNSUPPORTED, std::string(k) + ": spilled registers or scratch memory"};
-  }
-  return code;
-}
-const TraceKernels &trace_kernels(int dev) {
-  std::lock_guard<std::mutex> lk(g_trace_mu);
-  TraceKernels &t = g_trace[dev];
-  if (t.k_chain) return t;
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, dev));
-  std::string arch = prop.gcnArchName;
-  if (arch.find(':') != std::string::npos) arch = arch.substr(0, arch.find(':'));
-  const std::vector<char> code = trace_code(arch);
-  HIPCHK(hipModuleLoadData(&t.module, code.data()));
-  HIPCHK(hipModuleGetFunction(&t.k_finish, t.module, "rh_trace_finish_kernel"));
-  HIPCHK(hipModuleGetFunction(&t.k_chain, t.module, "rh_trace_chain_kernel"));
-  return t;
-}
-
-// the argument rules shared by the two entry points (before any device call, so that they hold on a machine without one)
-int trace_check_args(const char *fn, const void *draws, int32_t chains, int32_t iterations, int32_t nvars, int32_t first, int32_t count,
-                     const double *rhat, const double *ess) {
-  if (!draws || !rhat || !ess) { g_err = std::string(fn) + ": NULL argument"; return RH_E_INVALID; }
-  if (nvars < 1 || iterations < 0 || first < 0 || count < 2 || (int64_t)first + count > iterations) {
-    g_err = std::string(fn) + ": the window [first, first + count) must hold at least 2 of the completed iterations";
-    return RH_E_INVALID;
-  }
-  if (chains < 2) { g_err = "requirement failed: diagnostics requires multiple chains"; return RH_E_INVALID; }  // Trace.scala:12
-  return RH_OK;
-}
-
-// draws: device pointer on `dev`, [chains][iterations][nvars]; the launches go to `stream` and are waited for
-void trace_run(const void *draws, int dev, hipStream_t stream, int chains, long long iterations, int nvars, int first, int count,
-               double *rhat, double *ess, double *mean, double *var) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Fail{RH_E_DEVICE, "no HIP device available: the engine has no CPU fallback"};
-  if (dev < 0) HIPCHK(hipGetDevice(&dev));
-  if (dev >= ndev) throw Fail{RH_E_INVALID, "no such device"};
-  HIPCHK(hipSetDevice(dev));
-  const TraceKernels &K = trace_kernels(dev);
-  // parameters per chunk: the workspace [chunk][chains][RT_SL] stays under the cap; whole tiles where a tile fits
-  long long pc = kTraceWsCap / ((long long)chains * kTraceSlots * (long long)sizeof(double));
-  pc = std::max<long long>(1, std::min<long long>(pc, nvars));
-  if (pc >= kTraceTile) pc -= pc % kTraceTile;
-  DevBuf ws(sizeof(double) * (size_t)pc * chains * kTraceSlots), res(sizeof(double) * 4 * (size_t)nvars);
-  double *d_rhat = (double *)res.p, *d_ess = d_rhat + nvars, *d_mean = d_ess + nvars, *d_var = d_mean + nvars;
-  const double *d_draws = (const double *)draws;
-  double *d_ws = (double *)ws.p;
-  long long nv = nvars;
-  for (long long p0 = 0; p0 < nvars; p0 += pc) {
-    int p_lo = (int)p0, p_cnt = (int)std::min<long long>(pc, nvars - p0);
-    const long long tiles = (p_cnt + kTraceTile - 1) / kTraceTile;
-    if (tiles * chains > 0x7fffffffll) throw Fail{RH_E_UNSUPPORTED, "rh_diagnostics_device: too many chains for one launch"};
-    void *a1[] = {&d_draws, &iterations, &nv, &first, &count, &chains, &p_lo, &p_cnt, &d_ws};
-    launch(K.k_chain, (unsigned)(tiles * chains), kTraceBlock, stream, a1);
-    void *a2[] = {&d_ws, &chains, &count, &p_lo, &d_rhat, &d_ess, &d_mean, &d_var};
-    launch(K.k_finish, (unsigned)p_cnt, kTraceFinBlock, stream, a2);
-  }
-  std::vector<double> host(4 * (size_t)nvars);
-  HIPCHK(hipMemcpyAsync(host.data(), res.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  std::memcpy(rhat, host.data(), sizeof(double) * nvars);
-  std::memcpy(ess, host.data() + nvars, sizeof(double) * nvars);
-  if (mean) std::memcpy(mean, host.data() + 2 * (size_t)nvars, sizeof(double) * nvars);
-  if (var) std::memcpy(var, host.data() + 3 * (size_t)nvars, sizeof(double) * nvars);
-}
-}  // namespace
-
-extern "C" int rh_sampler_diagnostics(rh_sampler *s, int32_t first, int32_t count, double *rhat, double *ess, double *mean, double *var) {
-  if (!s) { g_err = "rh_sampler_diagnostics: NULL"; return RH_E_INVALID; }
-  const int rc0 = trace_check_args("rh_sampler_diagnostics", s->d_draws ? s->d_draws : (const void *)s, s->chains, s->it_done,
-                                   (int32_t)s->m->prog.n_params, first, count, rhat, ess);
-  if (rc0 != RH_OK) { s->m->err = g_err; return rc0; }
-  std::lock_guard<std::mutex> lk(s->m->mu);
-  // on the sampler's own stream, behind whatever it still has in flight; not part of rh_timing's figures (no events, no counters)
-  return guard(s->m, [&] {
-    trace_run(s->d_draws, s->m->device, s->m->stream, s->chains, s->cfg.iterations, (int)s->m->prog.n_params, first, count, rhat, ess, mean, var);
-  });
-}
-
-extern "C" int rh_diagnostics_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars,
-                                     int32_t first, int32_t count, double *rhat, double *ess, double *mean, double *var) {
-  const int rc0 = trace_check_args("rh_diagnostics_device", dev_draws, chains, iterations, nvars, first, count, rhat, ess);
-  if (rc0 != RH_OK) return rc0;
-  return guard(nullptr, [&] {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Fail{RH_E_DEVICE, "no HIP device available: the engine has no CPU fallback"};
-    if (device < 0) HIPCHK(hipGetDevice(&device));
-    if (device >= ndev) throw Fail{RH_E_INVALID, "rh_diagnostics_device: no such device"};
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipDeviceSynchronize());   // whoever filled the buffer (a sampler's stream, the RCCL gather) has finished
-    trace_run(dev_draws, device, nullptr, chains, iterations, nvars, first, count, rhat, ess, mean, var);
-  });
-}
-
-// No device needed: device/rh_trace.hip.h -> code object for `arch` (through the kernel cache), judged as before a launch.
-// *code_out: the code object (malloc'ed, the caller frees it with rh_free).  build() calls it so that the code object is in the
-// in-tree kernel cache; the CPU tests read the kernels' metadata from it.
-extern "C" int rh_trace_lower_only(const char *arch, void **code_out, size_t *code_size) {
-  return guard(nullptr, [&] {
-    const std::vector<char> code = trace_code(arch && *arch ? arch : "gfx950");
-    if (code_size) *code_size = code.size();
-    if (code_out) { *code_out = std::malloc(code.size()); std::memcpy(*code_out, code.data(), code.size()); }
-  });
-}
-
-// ---- Trace.predict / Trace.thin over device-resident draws (device/rh_predict.hip.h) ---------------------------------------------
-// rh_requirements_eval above uploads host draws and compiles on every call; a predictor is compiled once (kernel cache), judged
-// like a model's kernels, and evaluated where the draws are.  core/Trace.scala:23-41, core/Generator.scala:59-94.
-struct rh_predict {
-  int device = 0, nreq = 0, nvars = 0, nref = 0;
-  hipModule_t module = nullptr;
-  hipFunction_t k_flat = nullptr, k_gather = nullptr, k_direct = nullptr;
-  int tile_flat = 0, tile_gather = 0, tile_direct = 0;
-  void *d_out = nullptr, *d_err = nullptr;
-  size_t out_bytes = 0;
-  std::mutex mu;
-};
-namespace {
-// device/rh_predict.hip.h: RP_WAVE, RP_MAX_TILE, RP_LDS_DOUBLES, RP_TILE_FOR
-const int kPredWave = 64, kPredMaxTile = 256, kPredLdsDoubles = 8064;
-int pred_tile_for(int stride) {
-  const int rows = kPredLdsDoubles / stride;
-  return rows >= kPredMaxTile ? kPredMaxTile : rows / kPredWave * kPredWave;
-}
-struct PredictLowered {
-  std::string src;
-  std::vector<char> code;
-  int nreq = 0, nvars = 0, nref = 0;
-  std::vector<std::string> kernels;   // the kernels the source holds, all fit to run
-};
-// RIR -> source -> code object for `arch` (kernel cache) -> every kernel judged; throws what rh_predict_create returns
-void predict_lower(const void *rir, size_t rir_len, const rh_compile_opts *opts, const std::string &arch, PredictLowered &L, bool compile) {
-  rh::Program P; std::string err;
-  if (!rh::parse_rir(rir, rir_len, P, err)) throw Fail{RH_E_INVALID, err};
-  if (P.kind != 1) throw Fail{RH_E_INVALID, "not a requirements program (header kind != 1)"};
-  if (P.targets.empty()) throw Fail{RH_E_INVALID, "a requirements program without requirements"};
-  rh::EmitOptions eo;
-  if (opts) { eo.strict_math = opts->math_mode == RH_MATH_STRICT; eo.fp_contract = opts->fp_contract != 0; }
-  std::string defines, body;
-  std::vector<uint32_t> refs;
-  if (!rh::emit_predict(P, eo, defines, body, err, refs)) throw Fail{RH_E_UNSUPPORTED, err};
-  L.nreq = (int)P.targets.size(); L.nvars = (int)P.n_params; L.nref = (int)refs.size();
-  L.src = "// generated by rainier-hip: requirements program for device-resident draws\n" + defines + kSharedSrc + "\n" + kPreludeSrc + "\n" + body + kPredictSrc;
-  const bool gather = pred_tile_for(L.nref | 1) >= kPredWave, flat = pred_tile_for(L.nvars | 1) >= kPredWave && 2 * L.nref >= L.nvars;
-  if (flat) L.kernels.push_back("rh_predict_flat_kernel");
-  if (gather) L.kernels.push_back("rh_predict_gather_kernel"); else L.kernels.push_back("rh_predict_direct_kernel");
-  if (!compile) return;
-  L.code = build_source(arch, L.src, std::string(), ".predict.co");   // (kept apart from the models' *.hsaco, like the trace kernels)
-  for (const std::string &k : L.kernels) {
-    std::string why;
-    if (kernel_health(L.code, k, &why) != KH_OK)
-      throw Fail{RH_E_UNSUPPORTED, "the predict kernel is not fit to run: " + (why.empty() ? k + " is missing" : why)};
-    rh::KernelMeta km;
-    if (!rh::kernel_meta(L.code, k, km) || km.vgpr_spills != 0 || km.sgpr_spills != 0 || km.scratch_bytes != 0 || rh::kernel_touches_scratch(L.code, k) != 0)
-      throw Fail{RH_E_UNSUPPORTED, "the predict kernel is not fit to run: " + k + ": spilled registers or scratch memory"};
-  }
-}
-
-// the argument rules of the two entry points (before any device call, so that they hold on a machine without one)
-int predict_check_args(const char *fn, const rh_predict *p, const void *draws, int64_t chains, int64_t iterations, int64_t nvars, int32_t first,
-                       int32_t count, int32_t thin) {
-  if (!p || !draws) { g_err = std::string(fn) + ": NULL argument"; return RH_E_INVALID; }
-  if (chains < 1 || iterations < 0 || first < 0 || count < 1 || thin < 1 || (int64_t)first + count > iterations) {
-    g_err = std::string(fn) + ": the window [first, first + count) must hold at least 1 of the completed iterations, thin >= 1";
-    return RH_E_INVALID;
-  }
-  if (nvars != p->nvars) { g_err = std::string(fn) + ": the draws have " + std::to_string(nvars) + " parameters, the program reads " + std::to_string(p->nvars); return RH_E_INVALID; }
-  return RH_OK;
-}
-
-// draws: device pointer on p's device, [chains][iterations][nvars]; the launch goes to `stream` and is waited for
-void predict_run(rh_predict *p, const void *draws, hipStream_t stream, int chains, long long iterations, int first, int count, int thin,
-                 double *host_out, void **dev_out, int *lookup_err) {
-  HIPCHK(hipSetDevice(p->device));
-  const long long kept64 = ((long long)count + thin - 1) / thin;
-  int kept = (int)kept64;
-  const size_t need = sizeof(double) * (size_t)chains * (size_t)kept * (size_t)p->nreq;
-  if (need > p->out_bytes) {
-    if (p->d_out) { HIPCHK(hipFree(p->d_out)); p->d_out = nullptr; p->out_bytes = 0; }
-    HIPCHK(hipMalloc(&p->d_out, need));
-    p->out_bytes = need;
-  }
-  const bool flat = p->k_flat && thin == 1;
-  hipFunction_t fn = flat ? p->k_flat : (p->k_gather ? p->k_gather : p->k_direct);
-  const int tile = flat ? p->tile_flat : (p->k_gather ? p->tile_gather : p->tile_direct);
-  int ntiles = (kept + tile - 1) / tile;
-  if ((long long)ntiles * chains > 0x7fffffffll) throw Fail{RH_E_UNSUPPORTED, "predict: too many chains x iterations for one launch"};
-  HIPCHK(hipMemsetAsync(p->d_err, 0, sizeof(int), stream));
-  const double *d_draws = (const double *)draws;
-  double *d_out = (double *)p->d_out;
-  int *d_err = (int *)p->d_err;
-  void *args[] = {&d_draws, &iterations, &first, &thin, &kept, &ntiles, &d_out, &d_err};
-  launch(fn, (unsigned)((long long)ntiles * chains), (unsigned)tile, stream, args);
-  if (host_out) HIPCHK(hipMemcpyAsync(host_out, p->d_out, need, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(lookup_err, p->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (dev_out) *dev_out = p->d_out;
-}
-}  // namespace
-
-extern "C" int rh_predict_create(const void *rir, size_t rir_len, const rh_compile_opts *opts, rh_predict **out) {
-  if (!rir || !out) { g_err = "rh_predict_create: NULL argument"; return RH_E_INVALID; }
-  *out = nullptr;
-  std::unique_ptr<rh_predict> p(new rh_predict);
-  const int rc = guard(nullptr, [&] {
-    PredictLowered L;
-    predict_lower(rir, rir_len, opts, "", L, false);   // the argument errors first: they hold without a device
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Fail{RH_E_DEVICE, "no HIP device available: the engine has no CPU fallback"};
-    int dev = opts ? opts->device : -1;
-    if (dev < 0) HIPCHK(hipGetDevice(&dev));
-    if (dev >= ndev) throw Fail{RH_E_INVALID, "rh_predict_create: no such device"};
-    HIPCHK(hipSetDevice(dev));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
-    std::string arch = prop.gcnArchName;
-    if (arch.find(':') != std::string::npos) arch = arch.substr(0, arch.find(':'));
-    L = PredictLowered();
-    predict_lower(rir, rir_len, opts, arch, L, true);
-    p->device = dev; p->nreq = L.nreq; p->nvars = L.nvars; p->nref = L.nref;
-    HIPCHK(hipModuleLoadData(&p->module, L.code.data()));
-    for (const std::string &k : L.kernels) {
-      hipFunction_t f;
-      HIPCHK(hipModuleGetFunction(&f, p->module, k.c_str()));
-      if (k == "rh_predict_flat_kernel") { p->k_flat = f; p->tile_flat = pred_tile_for(L.nvars | 1); }
-      else if (k == "rh_predict_gather_kernel") { p->k_gather = f; p->tile_gather = pred_tile_for(L.nref | 1); }
-      else { p->k_direct = f; p->tile_direct = kPredWave; }
-    }
-    HIPCHK(hipMalloc(&p->d_err, sizeof(int)));
-  });
-  if (rc != RH_OK) { rh_predict_destroy(p.release()); return rc; }
-  *out = p.release();
-  return RH_OK;
-}
-
-extern "C" void rh_predict_destroy(rh_predict *p) {
-  if (!p) return;
-  if (p->module || p->d_out || p->d_err) {
-    (void)hipSetDevice(p->device);
-    if (p->d_out) (void)hipFree(p->d_out);
-    if (p->d_err) (void)hipFree(p->d_err);
-    if (p->module) (void)hipModuleUnload(p->module);
-  }
-  delete p;
-}
-extern "C" int rh_predict_nreq(const rh_predict *p) { return p ? p->nreq : -1; }
-extern "C" int rh_predict_nvars(const rh_predict *p) { return p ? p->nvars : -1; }
-
-extern "C" int rh_sampler_predict(rh_sampler *s, rh_predict *p, int32_t first, int32_t count, int32_t thin, double *host_out, void **dev_out) {
-  if (!s) { g_err = "rh_sampler_predict: NULL"; return RH_E_INVALID; }
-  int rc0 = predict_check_args("rh_sampler_predict", p, s->d_draws ? s->d_draws : (const void *)s, s->chains, s->it_done, (int64_t)s->m->prog.n_params,
-                               first, count, thin);
-  if (rc0 == RH_OK && p->device != s->m->device) { g_err = "rh_sampler_predict: the predictor and the sampler are on different devices"; rc0 = RH_E_INVALID; }
-  if (rc0 != RH_OK) { s->m->err = g_err; return rc0; }
-  std::lock_guard<std::mutex> lk(s->m->mu);
-  std::lock_guard<std::mutex> lp(p->mu);
-  int lookup_err = 0;
-  // on the sampler's own stream, behind whatever it still has in flight; reads the draws only; not part of rh_timing's figures
-  const int rc = guard(s->m, [&] {
-    predict_run(p, s->d_draws, s->m->stream, s->chains, s->cfg.iterations, first, count, thin, host_out, dev_out, &lookup_err);
-  });
-  if (rc == RH_OK && lookup_err) { g_err = "Lookup index out of range during evaluation"; s->m->err = g_err; return RH_E_LOOKUP; }
-  return rc;
-}
-
-extern "C" int rh_predict_device(rh_predict *p, const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars,
-                                 int32_t first, int32_t count, int32_t thin, double *host_out, void **dev_out) {
-  int rc0 = predict_check_args("rh_predict_device", p, dev_draws, chains, iterations, nvars, first, count, thin);
-  if (rc0 == RH_OK && device >= 0 && device != p->device) { g_err = "rh_predict_device: the predictor and the buffer are on different devices"; rc0 = RH_E_INVALID; }
-  if (rc0 != RH_OK) return rc0;
-  std::lock_guard<std::mutex> lp(p->mu);
-  int lookup_err = 0;
-  const int rc = guard(nullptr, [&] {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, dev_draws) == hipSuccess && at.type == hipMemoryTypeDevice && at.device != p->device)
-      throw Fail{RH_E_INVALID, "rh_predict_device: the predictor and the buffer are on different devices"};
-    (void)hipGetLastError();
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());   // whoever filled the buffer (a sampler's stream, the RCCL gather) has finished
-    predict_run(p, dev_draws, nullptr, chains, iterations, first, count, thin, host_out, dev_out, &lookup_err);
-  });
-  if (rc == RH_OK && lookup_err) { g_err = "Lookup index out of range during evaluation"; return RH_E_LOOKUP; }
-  return rc;
-}
-
-// No device needed (next to rh_lower_only): a requirements program -> the predict source and its code object for `arch`, through
-// the kernel cache, judged as rh_predict_create judges it.  *src_out / *code_out: malloc'ed, freed with rh_free; code_size NULL
-// stops after the lowering.  build() calls it so that the GPU tests' predictors come from the in-tree kernel cache.
-extern "C" int rh_lower_predict(const void *rir, size_t rir_len, const rh_compile_opts *opts, const char *arch, char **src_out,
-                                size_t *code_size, void **code_out) {
-  if (src_out) *src_out = nullptr;
-  if (code_out) *code_out = nullptr;
-  if (!rir) { g_err = "rh_lower_predict: NULL argument"; return RH_E_INVALID; }
-  return guard(nullptr, [&] {
-    PredictLowered L;
-    struct Keep { PredictLowered &L; char **src_out; ~Keep() { if (src_out && !L.src.empty()) { *src_out = (char *)std::malloc(L.src.size() + 1); std::memcpy(*src_out, L.src.c_str(), L.src.size() + 1); } } } keep{L, src_out};
-    predict_lower(rir, rir_len, opts, arch && *arch ? arch : "gfx950", L, code_size != nullptr);
-    if (code_size) *code_size = L.code.size();
-    if (code_out && code_size) { *code_out = std::malloc(L.code.size()); std::memcpy(*code_out, L.code.data(), L.code.size()); }
-  });
-}
-
-// ---- precis / hdpi over device-resident draws (device/rh_summary.hip.h) -------------------------------------------------------------
-// The reference sorts the pooled column of every parameter on the host (rainier-notebook package.scala:327-342, 367-418); here the
-// columns are sorted where the draws are -- tile sorts, merge passes between two workspace buffers, one finish workgroup per
-// parameter -- and only the figures come back.  One code object per architecture, cached and judged like the trace kernels'.
-namespace {
-const int kSumBlock = 256, kSumTile = 4096, kSumMergeTile = 2048, kSumMaxProbs = 16;   // RS_BLOCK, RS_TILE, RS_MERGE_TILE, RS_MAX_PROBS
-const long long kSumWsCap = 128ll << 20;                                               // RS_WS_CAP_BYTES
-struct SummaryKernels { hipModule_t module = nullptr; hipFunction_t k_sort = nullptr, k_merge = nullptr, k_finish = nullptr; };
-std::mutex g_summary_mu;
-std::map<int, SummaryKernels> g_summary;   // by device ordinal, kept for the process
-
-std::vector<char> summary_code(const std::string &arch) {
-  const std::vector<char> code = build_source(arch, std::string("// generated by rainier-hip: posterior summaries\n") + kSummarySrc, std::string(), ".summary.co");
-  for (const char *k : {"rh_summary_sort_kernel", "rh_summary_merge_kernel", "rh_summary_finish_kernel"}) {
-    std::string why;
-    if (kernel_health(code, k, &why) != KH_OK) throw Fail{RH_E_UNSUPPORTED, "the summary kernels are not fit to run on this toolchain: " + (why.empty() ? std::string(k) + " is missing" : why)};
-    rh::KernelMeta km;
-    if (!rh::kernel_meta(code, k, km) || km.vgpr_spills != 0 || km.sgpr_spills != 0 || km.scratch_bytes != 0 || rh::kernel_touches_scratch(code, k) != 0)
-      throw Fail{RH_E_UNSUPPORTED, std::string(k) + ": spilled registers or scratch memory"};
-  }
-  return code;
-}
-const SummaryKernels &summary_kernels(int dev) {
-  std::lock_guard<std::mutex> lk(g_summary_mu);
-  SummaryKernels &t = g_summary[dev];
-  if (t.k_sort) return t;
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, dev));
-  std::string arch = prop.gcnArchName;
-  if (arch.find(':') != std::string::npos) arch = arch.substr(0, arch.find(':'));
-  const std::vector<char> code = summary_code(arch);
-  HIPCHK(hipModuleLoadData(&t.module, code.data()));
-  HIPCHK(hipModuleGetFunction(&t.k_merge, t.module, "rh_summary_merge_kernel"));
-  HIPCHK(hipModuleGetFunction(&t.k_finish, t.module, "rh_summary_finish_kernel"));
-  HIPCHK(hipModuleGetFunction(&t.k_sort, t.module, "rh_summary_sort_kernel"));
-  return t;
-}
-
-// the argument rules shared by the two entry points (before any device call, so that they hold on a machine without one)
-int summary_check_args(const char *fn, const void *draws, int64_t chains, int64_t iterations, int64_t nvars, int32_t first, int32_t count,
-                       int32_t thin, const double *probs, int32_t nprobs, double hdpi_prob) {
-  const std::string f(fn);
-  if (!draws || !probs) { g_err = f + ": NULL argument"; return RH_E_INVALID; }
-  if (chains < 1 || nvars < 1 || iterations < 0 || first < 0 || count < 1 || thin < 1 || (int64_t)first + count > iterations) {
-    g_err = f + ": the window [first, first + count) must hold at least 1 of the completed iterations, thin >= 1";
-    return RH_E_INVALID;
-  }
-  if (nprobs < 1 || nprobs > kSumMaxProbs) { g_err = f + ": nprobs must be in 1 .. 16"; return RH_E_INVALID; }
-  for (int k = 0; k < nprobs; k++)
-    if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) { g_err = f + ": every probability must be in [0, 1]"; return RH_E_INVALID; }
-  if (!(hdpi_prob <= 1.0)) { g_err = f + ": hdpi_prob must be in (0, 1] (<= 0: not asked for)"; return RH_E_INVALID; }
-  return RH_OK;
-}
-
-// draws: device pointer on `dev` (an existing device: the caller's business), [chains][iterations][nvars]; the launches go to `stream`
-// and are waited for
-void summary_run(const void *draws, int dev, hipStream_t stream, int chains, long long iterations, int nvars, int first, int count, int thin,
-                 const double *probs, int nprobs, double hdpi_prob, double *mean, double *sd, double *quantiles, double *hdpi) {
-  long long kept = ((long long)count + thin - 1) / thin, N = (long long)chains * kept;
-  const long long per_param = 2 * N * (long long)sizeof(unsigned long long);   // the two ping-pong buffers
-  if (per_param > kSumWsCap)
-    throw Fail{RH_E_UNSUPPORTED, "summary: one pooled column of " + std::to_string(N) + " values needs " + std::to_string(per_param) +
-                                     " bytes of sort workspace, beyond the cap of " + std::to_string(kSumWsCap) + " (thin the window)"};
-  // the indices, on the host, in double (precis: data(math.floor(data.size * q).toInt); hdpi: math.ceil(prob * sorted.size).toInt)
-  long long idx[kSumMaxProbs] = {0};
-  for (int k = 0; k < nprobs; k++) idx[k] = std::min<long long>(N - 1, (long long)std::floor((double)N * probs[k]));
-  long long hidx = 0;
-  if (hdpi_prob > 0.0) hidx = std::max<long long>(1, std::min<long long>(N, (long long)std::ceil(hdpi_prob * (double)N)));
-  HIPCHK(hipSetDevice(dev));
-  const SummaryKernels &K = summary_kernels(dev);
-  const long long pc = std::max<long long>(1, std::min<long long>(kSumWsCap / per_param, nvars));
-  const size_t nres = (size_t)nvars * (size_t)(4 + nprobs);
-  DevBuf ws((size_t)per_param * (size_t)pc), res(sizeof(double) * nres), didx(sizeof idx);
-  HIPCHK(hipMemcpyAsync(didx.p, idx, sizeof idx, hipMemcpyHostToDevice, stream));
-  double *d_mean = (double *)res.p, *d_sd = d_mean + nvars, *d_hdpi = d_sd + nvars, *d_quant = d_hdpi + 2 * (size_t)nvars;
-  HIPCHK(hipMemsetAsync(res.p, 0, sizeof(double) * nres, stream));
-  const double *d_draws = (const double *)draws;
-  const long long *d_idx = (const long long *)didx.p;
-  const long long tiles = (N + kSumTile - 1) / kSumTile, mtiles = (N + kSumMergeTile - 1) / kSumMergeTile;
-  long long nv = nvars, first64 = first, thin64 = thin;
-  for (long long p0 = 0; p0 < nvars; p0 += pc) {
-    int p_lo = (int)p0, p_cnt = (int)std::min<long long>(pc, nvars - p0);
-    if (tiles * p_cnt > 0x7fffffffll || mtiles * p_cnt > 0x7fffffffll) throw Fail{RH_E_UNSUPPORTED, "summary: too many tiles for one launch"};
-    unsigned long long *src = (unsigned long long *)ws.p, *dst = src + (size_t)pc * (size_t)N;
-    void *a1[] = {&d_draws, &iterations, &nv, &first64, &thin64, &kept, &N, &p_lo, &p_cnt, &src};
-    launch(K.k_sort, (unsigned)(tiles * p_cnt), kSumBlock, stream, a1);
-    for (long long L = kSumTile; L < N; L *= 2) {
-      void *a2[] = {&src, &dst, &N, &L, &p_cnt};
-      launch(K.k_merge, (unsigned)(mtiles * p_cnt), kSumBlock, stream, a2);
-      std::swap(src, dst);
-    }
-    void *a3[] = {&src, &N, &d_idx, &nprobs, &hidx, &p_lo, &d_mean, &d_sd, &d_quant, &d_hdpi};
-    launch(K.k_finish, (unsigned)p_cnt, kSumBlock, stream, a3);
-  }
-  std::vector<double> host(nres);
-  HIPCHK(hipMemcpyAsync(host.data(), res.p, sizeof(double) * nres, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (mean) std::memcpy(mean, host.data(), sizeof(double) * nvars);
-  if (sd) std::memcpy(sd, host.data() + nvars, sizeof(double) * nvars);
-  if (hdpi && hidx > 0) std::memcpy(hdpi, host.data() + 2 * (size_t)nvars, sizeof(double) * 2 * nvars);
-  if (quantiles) std::memcpy(quantiles, host.data() + 4 * (size_t)nvars, sizeof(double) * (size_t)nvars * nprobs);
-}
-}  // namespace
-
-extern "C" int rh_sampler_summary(rh_sampler *s, int32_t first, int32_t count, int32_t thin, const double *probs, int32_t nprobs,
-                                  double hdpi_prob, double *mean, double *sd, double *quantiles, double *hdpi) {
-  if (!s) { g_err = "rh_sampler_summary: NULL"; return RH_E_INVALID; }
-  const int rc0 = summary_check_args("rh_sampler_summary", s->d_draws ? s->d_draws : (const void *)s, s->chains, s->it_done,
-                                     (int64_t)s->m->prog.n_params, first, count, thin, probs, nprobs, hdpi_prob);
-  if (rc0 != RH_OK) { s->m->err = g_err; return rc0; }
-  std::lock_guard<std::mutex> lk(s->m->mu);
-  // on the sampler's own stream, behind whatever it still has in flight; reads the draws only; not part of rh_timing's figures
-  return guard(s->m, [&] {
-    summary_run(s->d_draws, s->m->device, s->m->stream, s->chains, s->cfg.iterations, (int)s->m->prog.n_params, first, count, thin, probs,
-                nprobs, hdpi_prob, mean, sd, quantiles, hdpi);
-  });
-}
-
-extern "C" int rh_summary_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
-                                 int32_t count, int32_t thin, const double *probs, int32_t nprobs, double hdpi_prob, double *mean,
-                                 double *sd, double *quantiles, double *hdpi) {
-  const int rc0 = summary_check_args("rh_summary_device", dev_draws, chains, iterations, nvars, first, count, thin, probs, nprobs, hdpi_prob);
-  if (rc0 != RH_OK) return rc0;
-  return guard(nullptr, [&] {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Fail{RH_E_DEVICE, "no HIP device available: the engine has no CPU fallback"};
-    if (device < 0) HIPCHK(hipGetDevice(&device));
-    if (device >= ndev) throw Fail{RH_E_INVALID, "rh_summary_device: no such device"};
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipDeviceSynchronize());   // whoever filled the buffer (a sampler's stream, a predictor, the RCCL gather) has finished
-    summary_run(dev_draws, device, nullptr, chains, iterations, nvars, first, count, thin, probs, nprobs, hdpi_prob, mean, sd, quantiles, hdpi);
-  });
-}
-
-// No device needed: device/rh_summary.hip.h -> code object for `arch` (through the kernel cache), judged as before a launch.
-// *code_out: the code object (malloc'ed, the caller frees it with rh_free).  build() calls it so that the code object is in the
-// in-tree kernel cache; the CPU tests read the kernels' metadata from it.
-extern "C" int rh_summary_lower_only(const char *arch, void **code_out, size_t *code_size) {
-  return guard(nullptr, [&] {
-    const std::vector<char> code = summary_code(arch && *arch ? arch : "gfx950");
-    if (code_size) *code_size = code.size();
-    if (code_out) { *code_out = std::malloc(code.size()); std::memcpy(*code_out, code.data(), code.size()); }
-  });
 }

@@ -177,6 +177,42 @@ def test_sampler_diagnostics_big_mode_all_parameters():
     s.close(); m.close()
 
 
+# ---- 3. next to the other calls over device-resident draws --------------------------------------------------------------------------------
+def test_diagnostics_summary_and_predict_interleaved_on_one_device():
+    """The trace and the summary kernels come out of one per-device module cache (csrc/draws.cpp), first use and repeat use
+    interleaved: diagnostics, summary and predict (thin 3) of a sampler's draws, diagnostics and summary of the predictor's device
+    buffer, diagnostics again -- each the host emulation's bits, the last the first's.  Funnel(10), strict math, 2 chains,
+    HMC 50 + 20, L = 5."""
+    from tests import test_predict_device_cpu as P
+    from tests import test_summary_device_cpu as S
+
+    def bits(got):
+        diag, mean, var = got
+        return np.array([r for r, _ in diag]), np.array([e for _, e in diag]), mean, var
+
+    def same_summary(a, b):
+        return all(S.same_bits(u, v) for u, v in zip(tuple(a)[:4], tuple(b)[:4]))
+    rir, nreq = models.funnel_predict(10)
+    m = R.Model(models.funnel(10), device=0, math_mode=_capi.MATH_STRICT)
+    cfg = R.HMC(50, 20, 5)
+    cfg.massMatrixTuner = lambda: R.IdentityMassMatrixTuner()
+    s = R.Sampler(m, cfg, [123, 124])
+    s.warmup(); s.run(20)
+    x = s.draws()
+    d_first = bits(s.diagnostics(moments=True))
+    assert same_bits(d_first, emulate(x))
+    assert same_summary(s.summary(), S.emulate(x))
+    p = R.Predictor(rir, device=0, math_mode=_capi.MATH_STRICT)
+    values = s.predict(p, thin=3)
+    assert values.shape == (2, 7, nreq) and np.array_equal(values, P.emulate("funnel", x, thin=3))
+    ptr = s.predict(p, thin=3, to_host=False)
+    assert same_bits(bits(R.diagnostics_device(ptr, 2, 7, nreq, device=0, moments=True)), emulate(values))
+    assert same_summary(R.summary_device(ptr, 2, 7, nreq, device=0), S.emulate(values))
+    d_last = bits(s.diagnostics(moments=True))
+    assert same_bits(d_last, emulate(x)) and same_bits(d_last, d_first)
+    p.close(); s.close(); m.close()
+
+
 # ---- 4. the gathered buffer ---------------------------------------------------------------------------------------------------------------
 def test_comm_diagnostics_world_size_one_equals_the_samplers():
     spec = models.eight_schools()

@@ -89,7 +89,7 @@ static inline double rh_compare(double a, double b) { return a > b ? 1.0 : (a ==
 using std::exp; using std::log; using std::fabs;
 '''
 _DRIVER = r'''
-// the launch of predict_run (csrc/engine.cpp) and the kernels' index arithmetic, one workgroup after the other
+// the launch of predict_run (csrc/draws.cpp) and the kernels' index arithmetic, one workgroup after the other
 template <int FORM> static int rp_walk(const double *draws, int chains, long long iterations, int first, int count, int thin, double *out) {
   const int kept = (count + thin - 1) / thin, tile = rp_cfg<FORM>::TILE, ntiles = (kept + tile - 1) / tile;
   std::vector<double> lds(rp_lds<FORM>::DOUBLES);

@@ -195,31 +195,25 @@ def window(kept, thin):
 # ---- the device text on the host -----------------------------------------------------------------------------------------------------
 _DRIVER = r'''
 #include <vector>
-#include <cmath>
-#include <cstddef>
-// the launches of summary_run (csrc/engine.cpp) and the three kernels' index arithmetic, one workgroup after the other
+// summary_run's launches (csrc/draws.cpp) by its own plan (csrc/draws_plan.hpp; pc 0: the plan's chunk) and the kernels' index arithmetic, one workgroup after the other
 extern "C" int rs_emulate(const double *draws, int chains, long long iterations, long long nvars, long long first, long long count,
                           long long thin, long long pc, const double *probs, int nprobs, double hdpi_prob, double *mean, double *sd,
                           double *quant, double *hdpi, rs_key *sorted_out) {
-  const long long kept = (count + thin - 1) / thin, N = chains * kept;
-  long long idx[RS_MAX_PROBS] = {0};
-  for (int k = 0; k < nprobs; k++) { idx[k] = (long long)std::floor((double)N * probs[k]); if (idx[k] > N - 1) idx[k] = N - 1; }
-  long long hidx = 0;
-  if (hdpi_prob > 0.0) { hidx = (long long)std::ceil(hdpi_prob * (double)N); if (hidx > N) hidx = N; if (hidx < 1) hidx = 1; }
+  const rh_plan::Summary P = rh_plan::summary_plan(chains, count, thin, nvars, probs, nprobs, hdpi_prob);
+  const long long kept = P.kept, N = P.N;
+  if (pc == 0) pc = P.pc;
   std::vector<rs_key> ws((size_t)(2 * pc * N)), lds_sort(RS_TILE_SLOTS), lds_merge(RS_MERGE_LDS), lds_fin(3 * RS_BLOCK);
-  const long long tiles = (N + RS_TILE - 1) / RS_TILE, mtiles = (N + RS_MERGE_TILE - 1) / RS_MERGE_TILE;
-  int passes = 0;
   for (long long p0 = 0; p0 < nvars; p0 += pc) {
     const int p_lo = (int)p0, p_cnt = (int)(pc < nvars - p0 ? pc : nvars - p0);
     rs_key *src = ws.data(), *dst = src + pc * N;
-    for (long long bid = 0; bid < tiles * p_cnt; bid++) {
+    for (long long bid = 0; bid < P.tiles * p_cnt; bid++) {
       const long long t = bid / p_cnt, g0 = t * RS_TILE;
       const int pl = (int)(bid - t * p_cnt);
       rs_tile_sort(draws + first * nvars + p_lo + pl, iterations, nvars, thin, kept, N, g0, lds_sort.data(), src + (long long)pl * N + g0, RS_BLOCK);
     }
-    passes = 0;
-    for (long long L = RS_TILE; L < N; L *= 2, passes++) {
-      for (long long bid = 0; bid < mtiles * p_cnt; bid++) {
+    for (int k = 0; k < P.passes; k++) {
+      const long long L = P.run(k);
+      for (long long bid = 0; bid < P.mtiles * p_cnt; bid++) {
         const long long t = bid / p_cnt, o0 = t * RS_MERGE_TILE;
         const int pl = (int)(bid - t * p_cnt);
         rs_merge_tile(src + (long long)pl * N, dst + (long long)pl * N, N, L, o0, lds_merge.data(), RS_BLOCK);
@@ -228,50 +222,45 @@ extern "C" int rs_emulate(const double *draws, int chains, long long iterations,
     }
     for (int pl = 0; pl < p_cnt; pl++) {
       const int p = p_lo + pl;
-      rs_param_finish(src + (long long)pl * N, N, idx, nprobs, hidx, lds_fin.data(), mean + p, sd + p, quant + (long long)p * nprobs, hdpi + 2 * (long long)p, RS_BLOCK);
+      rs_param_finish(src + (long long)pl * N, N, P.idx, nprobs, P.hidx, lds_fin.data(), mean + p, sd + p, quant + (long long)p * nprobs, hdpi + 2 * (long long)p, RS_BLOCK);
       if (sorted_out) for (long long i = 0; i < N; i++) sorted_out[(long long)p * N + i] = src[(long long)pl * N + i];
     }
   }
-  return passes;
+  return P.passes;
 }
-extern "C" long long rs_ws_cap(void) { return RS_WS_CAP_BYTES; }
 extern "C" int rs_tile(void) { return RS_TILE; }
 extern "C" int rs_pair_lo_of(int i, int j) { return rs_pair_lo(i, j); }
 extern "C" int rs_slot_of(int e) { return RS_SLOT(e); }
-extern "C" int rs_merge_tile_size(void) { return RS_MERGE_TILE; }
 '''
 _emu = None
 
 
 def emulation():
-    """rh_summary.hip.h + the driver above as a host shared library (g++ -O2 -ffp-contract=off, as hiprtc is told for the device)"""
+    """draws_plan.hpp (which brings rh_summary.hip.h in host mode) + the driver above as a host shared library (g++ -O2 -ffp-contract=off, as hiprtc is told for the device)"""
     global _emu
     if _emu is None:
         import tempfile
         d = tempfile.mkdtemp(prefix="rh_summary_emu")
         src = os.path.join(d, "emu.cpp")
-        hdr = os.path.join(ROOT, "rainier_amd", "csrc", "device", "rh_summary.hip.h")
-        open(src, "w").write('#define RH_SUMMARY_HOST 1\n#include "%s"\n%s' % (hdr, _DRIVER))
+        hdr = os.path.join(ROOT, "rainier_amd", "csrc", "draws_plan.hpp")
+        open(src, "w").write('#include "%s"\n%s' % (hdr, _DRIVER))
         so = os.path.join(d, "emu.so")
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-shared", "-fPIC", src, "-o", so])
         L = C.CDLL(so)
         dp, ll = C.POINTER(C.c_double), C.c_longlong
         L.rs_emulate.argtypes = [dp, C.c_int, ll, ll, ll, ll, ll, ll, dp, C.c_int, C.c_double, dp, dp, dp, dp, C.POINTER(C.c_uint64)]
-        L.rs_ws_cap.restype = ll
         _emu = L
     return _emu
 
 
-def emulate(x, first=0, count=None, thin=1, probs=PROBS, hdpi=HDPI, pc=None, passes=False):
+def emulate(x, first=0, count=None, thin=1, probs=PROBS, hdpi=HDPI, pc=0, passes=False):
     """the host emulation over x [chains][iterations][nvars] -> mean, sd, quantiles, hdpi, sorted keys [nvars][N];
-    pc: parameters per chunk (None: the engine's rule)"""
+    pc: parameters per chunk (0: the engine's)"""
     L = emulation()
     x = np.ascontiguousarray(x, dtype=np.float64)
     m, iters, k = x.shape
     count = iters - first if count is None else count
     n = m * (-(-count // thin))
-    if pc is None:
-        pc = max(1, min(L.rs_ws_cap() // (16 * n), k))
     pr = np.array(probs, dtype=np.float64)
     mean, sd, quant, hd = np.full(k, -1.0), np.full(k, -1.0), np.full((k, len(pr)), -1.0), np.full((k, 2), -1.0)
     keys = np.zeros((k, n), dtype=np.uint64)

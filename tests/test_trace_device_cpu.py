@@ -83,14 +83,14 @@ def check_against_oracle(x, rhat, ess, what, cols=None):
 # ---- the device text on the host ---------------------------------------------------------------------------------------------------
 _DRIVER = r'''
 #include <vector>
-#include <cstddef>
-// the launches of trace_run (csrc/engine.cpp) and the two kernels' index arithmetic, one workgroup after the other
+// trace_run's launches (csrc/draws.cpp) by its own plan (csrc/draws_plan.hpp; pc 0: the plan's chunk) and the kernels' index arithmetic, one workgroup after the other
 extern "C" void rt_emulate(const double *draws, int chains, long long iterations, long long nvars, int first, int n, long long pc,
                            double *rhat, double *ess, double *mean, double *var) {
+  if (pc == 0) pc = rh_plan::trace_chunk(chains, (int)nvars);
   std::vector<double> ws((size_t)pc * chains * RT_SL), lds(RT_LDS_DOUBLES + RT_TP), lds2(RT_SL + RT_FIN_BLOCK);
   for (long long p0 = 0; p0 < nvars; p0 += pc) {
     const int p_lo = (int)p0, p_cnt = (int)(pc < nvars - p0 ? pc : nvars - p0);
-    const int tiles = (p_cnt + RT_TP - 1) / RT_TP;
+    const int tiles = (int)rh_plan::trace_tiles(p_cnt);
     for (int tile = 0; tile < tiles; tile++)
       for (int c = 0; c < chains; c++) {
         const int pl = tile * RT_TP;
@@ -104,43 +104,35 @@ extern "C" void rt_emulate(const double *draws, int chains, long long iterations
     }
   }
 }
-extern "C" long long rt_ws_cap(void) { return RT_WS_CAP_BYTES; }
-extern "C" int rt_slots(void) { return RT_SL; }
-extern "C" int rt_tile(void) { return RT_TP; }
 '''
 _emu = None
 
 
 def emulation():
-    """rh_trace.hip.h + the driver above as a host shared library (g++ -O2 -ffp-contract=off: every a*b+c stays two roundings,
+    """draws_plan.hpp (which brings rh_trace.hip.h in host mode) + the driver above as a host shared library (g++ -O2 -ffp-contract=off: every a*b+c stays two roundings,
     as hiprtc is told for the device)"""
     global _emu
     if _emu is None:
         import tempfile
         d = tempfile.mkdtemp(prefix="rh_trace_emu")
         src = os.path.join(d, "emu.cpp")
-        hdr = os.path.join(ROOT, "rainier_amd", "csrc", "device", "rh_trace.hip.h")
-        open(src, "w").write('#define RH_TRACE_HOST 1\n#include "%s"\n%s' % (hdr, _DRIVER))
+        hdr = os.path.join(ROOT, "rainier_amd", "csrc", "draws_plan.hpp")
+        open(src, "w").write('#include "%s"\n%s' % (hdr, _DRIVER))
         so = os.path.join(d, "emu.so")
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-shared", "-fPIC", src, "-o", so])
         L = C.CDLL(so)
         dp = C.POINTER(C.c_double)
         L.rt_emulate.argtypes = [dp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_longlong, dp, dp, dp, dp]
-        L.rt_ws_cap.restype = C.c_longlong
         _emu = L
     return _emu
 
 
-def emulate(x, first=0, count=None, pc=None):
-    """the host emulation over x [chains][iterations][nvars] -> rhat, ess, mean, var; pc: parameters per chunk (None: the engine's)"""
+def emulate(x, first=0, count=None, pc=0):
+    """the host emulation over x [chains][iterations][nvars] -> rhat, ess, mean, var; pc: parameters per chunk (0: the engine's)"""
     L = emulation()
     x = np.ascontiguousarray(x, dtype=np.float64)
     m, iters, k = x.shape
     count = iters - first if count is None else count
-    if pc is None:
-        pc = max(1, min(L.rt_ws_cap() // (m * L.rt_slots() * 8), k))
-        if pc >= L.rt_tile():
-            pc -= pc % L.rt_tile()
     out = [np.full(k, -1.0) for _ in range(4)]
     L.rt_emulate(_capi.dptr(x), m, iters, k, first, count, pc, *[_capi.dptr(o) for o in out])
     return out

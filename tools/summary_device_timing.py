@@ -22,7 +22,7 @@ hip = C.CDLL("/opt/rocm/lib/libamdhip64.so")
 hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
 hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
 hip.hipFree.argtypes = [C.c_void_p]
-TILE = 4096              # RS_TILE
+TILE = 4096              # RS_TILE (csrc/device/rh_summary.hip.h)
 
 
 def median5(fn):
