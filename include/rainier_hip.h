@@ -39,7 +39,8 @@ extern "C" {
                              4: rh_model_clone;
                              5: rh_model_engines, rh_compile_count;
                              6: rh_timing.chain_slots / steady_* (the tick engine's gradient launches serve the live chains only);
-                                (still 6, additions only: rh_sampler_diagnostics, rh_diagnostics_device) */
+                                (still 6, additions only: rh_sampler_diagnostics, rh_diagnostics_device, rh_predict_*, rh_*_summary*, rh_generate_*,
+                                 rh_sampler_generate) */
 
 enum rh_status {
   RH_OK = 0,
@@ -353,6 +354,65 @@ int rh_sampler_summary(rh_sampler *s, int32_t first, int32_t count, int32_t thin
 int rh_summary_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
                       int32_t count, int32_t thin, const double *probs, int32_t nprobs, double hdpi_prob, double *mean, double *sd,
                       double *quantiles, double *hdpi);
+
+/* ---- posterior-predictive sampling over device-resident draws: Trace.predict of a Distribution ------------------------------
+ * In the reference trace.predict(value) takes any ToGenerator -- a Real, but also a Distribution (core/Trace.scala:34-41,
+ * core/Generator.scala:171-174): trace.predict(Normal(mu, sigma)) returns posterior-predictive samples, and SBC.synthesize is the
+ * same machinery (core/SBC.scala:53-61).  rh_predict is the deterministic half (the compiled requirements); this is the sampling
+ * half (csrc/device/rh_generate.hip.h): a model-independent kernel that turns a device buffer of per-draw distribution parameters
+ * in [chains][kept][nin] into per-draw samples out [chains][kept][nout], the layout rh_summary_device / rh_diagnostics_device read.
+ * A generator is a table of ops, given as data; output o of flat row r = c * kept + j is out[r * nout + o], nout = nops.
+ * Every draw runs the reference's Generator.get(rng, evaluator) on a java.util.Random stream of its own: global draw index
+ * d = chain0 * kept + r (unsigned 64-bit; chain0: the global id of the buffer's first chain, so that a shard of a multi-GPU run
+ * draws what the whole run would), seed_d = splitmix64's finaliser of seed + (d + 1) * 0x9E3779B97F4A7C15, stream
+ * new java.util.Random(seed_d).  The ops of a draw run left to right on that stream (Generator.zip / traverse,
+ * Generator.scala:38-47, 145-150), the pending nextNextGaussian carried along.  The results do not depend on tiling or sharding.
+ * java.lang.Math follows the oracle's JM_DET policy (fdlibm log / exp, IEEE sqrt; Gamma's Math.pow(u, 1 / a) is
+ * exp((1 / a) * log(u))), so every family is bit-comparable.  u = standardUniform, g = standardNormal, * and + separate:
+ *   RH_GEN_REAL      a             a                                            Generator.scala:119-122
+ *   RH_GEN_NORMAL    loc, scale    g * scale + loc                              Continuous.scala:54-57, 63-67; Injection.scala:50-52, 70-72
+ *   RH_GEN_CAUCHY    loc, scale    (g1 / g2) * scale + loc                      Continuous.scala:72-77
+ *   RH_GEN_LAPLACE   loc, scale    x * scale + loc, x = (signum(u') * -1) * log(1 - 2 * abs(u')), u' = u - 0.5      :82-89
+ *   RH_GEN_UNIFORM   loc, scale    u * scale + loc   (scale = to - from)        :202-215
+ *   RH_GEN_LOGNORMAL loc, scale    exp(g * scale + loc)                         :194-197; Injection.scala:89-91
+ *   RH_GEN_GAMMA     shape, scale  Marsaglia-Tsang with the a < 1 boost, * scale                                    :94-147
+ *   RH_GEN_BETA      a, b          z1 / (z1 + z2), z1 = gamma(a) * 1.0, then z2 = gamma(b) * 1.0                    :163-176
+ *   RH_GEN_BERNOULLI p             u <= p ? 1 : 0                               Discrete.scala:38-48
+ *   RH_GEN_GEOMETRIC p             (double)(long)floor(log(u) / log(1 - p))     :59-69
+ *   RH_GEN_POISSON   lambda        Poisson.small below 30, else Poisson.large   :122-186
+ * (Exponential(rate) is RH_GEN_GAMMA(1.0, 1 / rate), Continuous.scala:152-158.)  .toLong is Java's d2l; every output is a double.
+ * No parameter can make a loop endless: GAMMA / BETA need every shape finite and > 0 and POISSON lambda finite and >= 0, else the
+ * output is NaN, the op draws nothing from the stream and the call reports RH_GEN_F_DOMAIN; every rejection loop stops after 4096
+ * passes with NaN and RH_GEN_F_CAP.  The return code stays RH_OK when a flag is set: the NaNs mark the samples. */
+enum rh_gen_family { RH_GEN_REAL = 0, RH_GEN_NORMAL = 1, RH_GEN_CAUCHY = 2, RH_GEN_LAPLACE = 3, RH_GEN_UNIFORM = 4, RH_GEN_LOGNORMAL = 5,
+                     RH_GEN_GAMMA = 6, RH_GEN_BETA = 7, RH_GEN_BERNOULLI = 8, RH_GEN_GEOMETRIC = 9, RH_GEN_POISSON = 10 };
+#define RH_GEN_F_DOMAIN 1
+#define RH_GEN_F_CAP 2
+typedef struct rh_gen_arg { int32_t col; int32_t pad; double value; } rh_gen_arg;  /* col >= 0: column of `in`; col == -1: `value` */
+typedef struct rh_gen_op  { int32_t family; int32_t reserved; rh_gen_arg a, b; } rh_gen_op;
+typedef struct rh_generate rh_generate;
+/* A generator as a table (what Generator.zip / traverse compose, core/Generator.scala:38-47, 145-150).  Validates without a device and
+ * touches none: nops in 1 .. 4096, nin >= 0, a known family, every col in -1 .. nin-1, the second
+ * argument of the one-argument families (REAL, BERNOULLI, GEOMETRIC, POISSON) unused (col -1, value 0); otherwise RH_E_INVALID with
+ * a message that names the op.  device: where the generator will run (-1: the device of its first call). */
+int rh_generate_create(const rh_gen_op *ops, int32_t nops, int32_t nin, int32_t device, rh_generate **out);
+void rh_generate_destroy(rh_generate *g);
+/* the outputs per draw (= nops: one sample per op, as Generator.traverse returns one value per generator, Generator.scala:145-150) */
+int rh_generate_nout(const rh_generate *g);
+/* Trace.predict's sampling (Trace.scala:34-41) over any device buffer dev_in [chains][kept][nin] on `device` (-1: the handle's), e.g. a
+ * predictor's *dev_out: on the null stream, synchronising the device before and after.  nin must be the handle's; a buffer on
+ * another device is refused.  host_out (may be NULL): caller-allocated [chains][kept][nout]; *dev_out (may be NULL): the generator's
+ * own buffer, valid until its next call; *flags (may be NULL): RH_GEN_F_* of the whole call.  No device: RH_E_DEVICE. */
+int rh_generate_device(rh_generate *g, const void *dev_in, int32_t device, int32_t chains, int32_t kept, int32_t nin,
+                       int64_t seed, int64_t chain0, double *host_out, void **dev_out, int32_t *flags);
+/* trace.predict(distribution) over the sampler's own draws (Trace.scala:34-41, Generator.scala:171-174): rh_sampler_predict's window
+ * through p, then g over p's output, on the sampler's stream with one synchronisation; the predictions stay in p's buffer.  p's nreq
+ * must be g's nin and the three objects on one device, else RH_E_INVALID. */
+int rh_sampler_generate(rh_sampler *s, rh_predict *p, rh_generate *g, int32_t first, int32_t count, int32_t thin,
+                        int64_t seed, int64_t chain0, double *host_out, void **dev_out, int32_t *flags);
+/* No device needed: the sampling kernel's code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a launch
+ * (the generators of core/Continuous.scala:54-215 and core/Discrete.scala:38-186 above); *code_out is malloc'ed, freed with rh_free. */
+int rh_generate_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */

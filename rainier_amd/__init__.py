@@ -6,7 +6,7 @@
   models.py        the BASELINE.json configurations as RIR + synthetic data
 """
 from .sampler import (DefaultConfig, DenseMassMatrixTuner, DensityFunction, DiagonalMassMatrix, DiagonalMassMatrixTuner,  # noqa: F401
-                      DualAvgTuner, EHMC, EHMCSampler, HMC, HMCSampler, IdentityMassMatrixTuner, Model, NUTSSampler, Predictor,
+                      DualAvgTuner, EHMC, EHMCSampler, Generator, HMC, HMCSampler, IdentityMassMatrixTuner, Model, NUTSSampler, Predictor,
                       RainierHipError, Sampler, SamplerConfig, StaticMassMatrix, StaticStepSize, Summary, Trace,
-                      diagnostics, diagnostics_device, format_precis, make_config, predict, predict_device, sample_multi,
+                      diagnostics, diagnostics_device, format_precis, gen, generate_device, make_config, predict, predict_device, sample_multi,
                       summary_device)

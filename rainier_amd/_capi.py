@@ -34,13 +34,25 @@ EXPORTS = [
     "rh_predict_create", "rh_predict_destroy", "rh_predict_nreq", "rh_predict_nvars", "rh_sampler_predict", "rh_predict_device",
     # precis / hdpi over device-resident draws (rainier-notebook package.scala:327-342, 367-418)
     "rh_sampler_summary", "rh_summary_device",
+    # Trace.predict of a Distribution over device-resident draws (core/Trace.scala:34-41, core/Generator.scala:171-174)
+    "rh_generate_create", "rh_generate_destroy", "rh_generate_nout", "rh_generate_device", "rh_sampler_generate", "rh_generate_lower_only",
 ]
+GEN_REAL, GEN_NORMAL, GEN_CAUCHY, GEN_LAPLACE, GEN_UNIFORM, GEN_LOGNORMAL, GEN_GAMMA, GEN_BETA, GEN_BERNOULLI, GEN_GEOMETRIC, GEN_POISSON = range(11)
+GEN_F_DOMAIN, GEN_F_CAP = 1, 2
 
 
 class CompileOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("math_mode", C.c_int32),
                 ("fp_contract", C.c_int32), ("rows_unroll", C.c_int32), ("grad_chains", C.c_int32),
                 ("grad_unroll", C.c_int32), ("factor_outputs", C.c_int32), ("with_nuts", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GenArg(C.Structure):      # rh_gen_arg: col >= 0: column of the input buffer; col == -1: `value`
+    _fields_ = [("col", C.c_int32), ("pad", C.c_int32), ("value", C.c_double)]
+
+
+class GenOp(C.Structure):       # rh_gen_op
+    _fields_ = [("family", C.c_int32), ("reserved", C.c_int32), ("a", GenArg), ("b", GenArg)]
 
 
 class Config(C.Structure):
@@ -127,6 +139,12 @@ def lib():
     L.rh_summary_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32, C.c_double,
                                     dp, dp, dp, dp]
     L.rh_summary_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_generate_create.argtypes = [C.POINTER(GenOp), C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.rh_generate_destroy.restype = None; L.rh_generate_destroy.argtypes = [vp]
+    L.rh_generate_nout.argtypes = [vp]
+    L.rh_generate_device.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, dp, C.POINTER(vp), C.POINTER(C.c_int32)]
+    L.rh_sampler_generate.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, dp, C.POINTER(vp), C.POINTER(C.c_int32)]
+    L.rh_generate_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_comm_unique_id.argtypes = [C.c_char_p]
     L.rh_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.rh_comm_destroy.argtypes = [vp]
@@ -275,6 +293,18 @@ def summary_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_summary_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def generate_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_generate.hip.h (posterior-predictive sampling on the device, behind the prelude) -> code object for `arch`,
+    without a device: compiled through the kernel cache and judged as before a launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_generate_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, which predict kernel.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -12,6 +12,11 @@
 #define RH_SUMMARY_HOST 1
 #include "device/rh_trace.hip.h"
 #include "device/rh_summary.hip.h"
+// rh_generate.hip.h's routine needs the prelude's rng around it: the CPU test's driver defines RH_GENERATE_HOST with one in place
+#ifndef RH_GENERATE_HOST
+#define RG_CONSTANTS_ONLY 1
+#endif
+#include "device/rh_generate.hip.h"
 namespace rh_plan {
 // ---- trace diagnostics (device/rh_trace.hip.h) ----
 // parameters per chunk: the workspace [chunk][chains][RT_SL] stays under the cap; whole tiles where a tile fits
@@ -65,5 +70,11 @@ inline PredictLaunch predict_launch(int nvars, int nref, int thin) {
   if (pred_has_gather(nref)) return {PRED_GATHER, pred_tile_for(nref | 1)};
   return {PRED_DIRECT, kPredWave};
 }
+// ---- posterior-predictive sampling (device/rh_generate.hip.h) ----
+// one workgroup per RG_TILE flat rows; the results leave through LDS in slabs of at most RG_SLAB ops
+inline long long generate_tiles(long long nrows) { return (nrows + RG_TILE - 1) / RG_TILE; }
+inline int generate_slab(int nops) { return RG_SLAB_W(nops); }                       // ops per slab
+inline int generate_slabs(int nops) { return (nops + generate_slab(nops) - 1) / generate_slab(nops); }
+inline size_t generate_lds_bytes(int nops) { return sizeof(double) * (size_t)RG_TILE * (size_t)RG_STRIDE(nops); }   // the launch's dynamic LDS
 }  // namespace rh_plan
 #endif

@@ -306,6 +306,101 @@ def predict_device(predictor: Predictor, ptr: int, chains: int, iterations: int,
     return _predict_result(call, predictor, int(chains), count, thin, int(device), to_host, diagnostics)
 
 
+class gen:
+    """Op constructors of a Generator's table (rh_gen_op): the reference's generators that Trace.predict accepts as a Distribution
+    (core/Trace.scala:34-41, core/Generator.scala:171-174).  Each argument is a gen.col(i) -- column i of the per-draw parameter
+    buffer, e.g. requirement i of a predictor -- or a float.  Uniform(from, to) passes the kernel scale = to - from and
+    Exponential(rate) passes 1 / rate, which this front end computes only from floats: with columns the caller supplies the SCALE
+    column itself (Uniform(from, scale_column), Exponential(scale_column)), e.g. as one more requirement of the predictor."""
+
+    class col(NamedTuple):
+        index: int
+
+    @staticmethod
+    def _arg(x) -> "_capi.GenArg":
+        return _capi.GenArg(int(x.index), 0, 0.0) if isinstance(x, gen.col) else _capi.GenArg(-1, 0, float(x))
+
+    @staticmethod
+    def _op(family, a, b=0.0) -> "_capi.GenOp":
+        return _capi.GenOp(family, 0, gen._arg(a), gen._arg(b))
+
+    @staticmethod
+    def Real(a): return gen._op(_capi.GEN_REAL, a)                                      # Generator.scala:119-122
+    @staticmethod
+    def Normal(location, scale): return gen._op(_capi.GEN_NORMAL, location, scale)     # Continuous.scala:63-67
+    @staticmethod
+    def Cauchy(location, scale): return gen._op(_capi.GEN_CAUCHY, location, scale)     # :72-77
+    @staticmethod
+    def Laplace(location, scale): return gen._op(_capi.GEN_LAPLACE, location, scale)   # :82-89
+    @staticmethod
+    def LogNormal(location, scale): return gen._op(_capi.GEN_LOGNORMAL, location, scale)   # :194-197
+    @staticmethod
+    def Gamma(shape, scale): return gen._op(_capi.GEN_GAMMA, shape, scale)             # :94-147
+    @staticmethod
+    def Beta(a, b): return gen._op(_capi.GEN_BETA, a, b)                                # :163-176
+    @staticmethod
+    def Bernoulli(p): return gen._op(_capi.GEN_BERNOULLI, p)                            # Discrete.scala:38-48
+    @staticmethod
+    def Geometric(p): return gen._op(_capi.GEN_GEOMETRIC, p)                            # :59-69
+    @staticmethod
+    def Poisson(lam): return gen._op(_capi.GEN_POISSON, lam)                            # :122-186
+
+    @staticmethod
+    def Uniform(from_, to):                                                             # Continuous.scala:202-215
+        """to: a float with a float `from_` (scale = to - from_); with a column on either side `to` IS the scale: float or column"""
+        if isinstance(from_, gen.col) or isinstance(to, gen.col):
+            return gen._op(_capi.GEN_UNIFORM, from_, to)
+        return gen._op(_capi.GEN_UNIFORM, from_, float(to) - float(from_))
+
+    @staticmethod
+    def Exponential(rate):                                                              # Continuous.scala:152-158
+        """rate: a float (scale = 1 / rate); a column is taken as the SCALE 1 / rate itself"""
+        return gen._op(_capi.GEN_GAMMA, 1.0, rate if isinstance(rate, gen.col) else 1.0 / float(rate))
+
+
+class Generator:
+    """rh_generate: a table of gen.* ops over `nin` per-draw parameter columns, for posterior-predictive samples of draws that stay on
+    the device (Sampler.generate, generate_device).  Output o of a draw is op o's sample; every draw has a java.util.Random stream
+    of its own and runs its ops left to right on it.  flags: GEN_F_DOMAIN | GEN_F_CAP of the last call (NaN samples mark the draws)."""
+
+    def __init__(self, ops, nin: int, device: int = -1):
+        self._h = C.c_void_p()
+        ops = list(ops)
+        arr = (_capi.GenOp * max(1, len(ops)))(*ops)
+        _capi.check(_capi.lib().rh_generate_create(arr, len(ops), int(nin), int(device), C.byref(self._h)))
+        self.nin = int(nin)
+        self.nout = _capi.lib().rh_generate_nout(self._h)
+        self.flags = 0
+
+    def close(self):
+        if self._h:
+            _capi.lib().rh_generate_destroy(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+
+
+def _generate_result(call, generator, chains, kept, to_host, model=None):
+    """shared by Sampler.generate and generate_device: call(host_out or None, byref(dev_out), byref(flags)) -> rc"""
+    out = np.zeros((chains, kept, generator.nout)) if to_host else None
+    ptr, flags = C.c_void_p(), C.c_int32(0)
+    _capi.check(call(_capi.dptr(out) if to_host else None, C.byref(ptr), C.byref(flags)), model)
+    generator.flags = int(flags.value)
+    return out if to_host else ptr.value
+
+
+def generate_device(generator: Generator, ptr: int, chains: int, kept: int, nin: int, seed: int, chain0: int = 0, device: int = 0,
+                    to_host: bool = True):
+    """Posterior-predictive samples over a device buffer [chains][kept][nin] of per-draw distribution parameters (a predictor's
+    to_host = False result): draw r = c * kept + j samples on the stream of global draw chain0 * kept + r, so a shard whose first
+    chain is chain0 draws what the whole run would.  Returns [chains][kept][nout] (to_host = False: the device pointer of the
+    generator's own buffer, valid until its next call -- what summary_device / diagnostics_device take)."""
+    call = lambda host, dev, fl: _capi.lib().rh_generate_device(generator._h, C.c_void_p(ptr), int(device), int(chains), int(kept), int(nin),
+                                                                int(seed), int(chain0), host, dev, fl)
+    return _generate_result(call, generator, int(chains), int(kept), to_host)
+
+
 class Summary(NamedTuple):
     """precis / hdpi of every parameter (rainier-notebook package.scala:327-342, 367-418): mean [nvars], sd [nvars] (population
     form), quantiles [nvars][nprobs] (the order statistics at floor(N * q)), hdpi [nvars][2] (None when not asked for), and the
@@ -420,6 +515,16 @@ class Sampler:
         call = lambda host, dev: _capi.lib().rh_sampler_predict(self._h, predictor._h, int(first), count, int(thin), host, dev)
         # (device -1: the current one, which rh_sampler_predict has just made the sampler's)
         return _predict_result(call, predictor, self.chains, count, thin, -1, to_host, diagnostics, self.model._h)
+
+    def generate(self, predictor: Predictor, generator: Generator, seed: int, first: int = 0, count: Optional[int] = None, thin: int = 1,
+                 chain0: int = 0, to_host: bool = True):
+        """trace.predict(distribution) over the draws where they are (rh_sampler_generate): the predictor's requirements of the kept
+        iterations first + j * thin are the generator's parameter columns.  Returns the samples [chains][kept][nout] (to_host =
+        False: the device pointer of the generator's buffer, which summary_device / diagnostics_device take)."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda host, dev, fl: _capi.lib().rh_sampler_generate(self._h, predictor._h, generator._h, int(first), count, int(thin),
+                                                                     int(seed), int(chain0), host, dev, fl)
+        return _generate_result(call, generator, self.chains, _kept(count, thin), to_host, self.model._h)
 
     def summary(self, first: int = 0, count: Optional[int] = None, thin: int = 1, probs: Sequence[float] = (0.055, 0.945),
                 hdpi: Optional[float] = 0.89) -> Summary:
