@@ -33,6 +33,7 @@
 #include "rir.hpp"
 #include "optimize.hpp"
 #include "engine_internal.hpp"
+#include "lanes_plan.hpp"
 
 // device sources embedded at build time (see Makefile: device_src.inc)
 const char *const kSharedSrc =
@@ -187,6 +188,33 @@ struct rh_model {
 
 namespace { struct GatherBufs; }
 
+// Tick engine: what one chain population needs to advance on its own.  A sampler has one lane, or two that part its chains on a
+// chain-group boundary (lanes_plan.hpp) and run on two streams: chains never interact, and while one lane sits between two
+// launches, in a tick or in a launch's prologue, the other lane's gradient launch has the fp64 pipe.  The per-chain arrays (state,
+// seeds, draws, stats, qbuf, active, records) stay the sampler's single allocations; a lane holds views at its first chain, and its
+// kernels number the chains from there (lists, partial sums and scatter sums are lane-local).
+struct Lane {
+  int first = 0, chains = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;         // (lane 0 runs on the model's stream)
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  std::vector<hipEvent_t> ev;
+  void *d_running = nullptr, *d_list = nullptr, *d_nlive = nullptr, *d_graderr = nullptr;
+  void *d_livelog = nullptr;       // [257] live counts logged by rh_compact_kernel, one per tick of a batch (+ the call's first tick)
+  void *d_partial = nullptr, *d_partial2 = nullptr;   // (the second one: fused launches)
+  int pp = 0;                      // which of the two partial-sum / record buffers the next launch writes
+  int cur_live = 0;                // chains in the list the next gradient launch serves
+  GatherBufs *gb = nullptr;
+  // views into the sampler's arrays at chain `first`
+  void *state = nullptr, *seeds = nullptr, *draws = nullptr, *stats = nullptr, *qbuf = nullptr, *active = nullptr, *rec[2] = {nullptr, nullptr};
+  // host side of a batch in flight
+  int running = 0, B = 0, remaining_hint = 32;
+  long long pos = 0;               // gradient launches since the first tick of this call
+  bool live = false;               // still advancing in this call
+  std::vector<int> livelog;
+  std::vector<char> was_ticked;
+};
+
 struct rh_sampler {
   hipFunction_t k_chain = nullptr, k_tick = nullptr;
   int state_words = 0, dense_off = 0, pack_l = 64;  // pack_l: lanes per chain of the chosen chain kernel
@@ -202,20 +230,15 @@ struct rh_sampler {
   // live-chain accounting of the tick engine's gradient launches (rh_timing.chain_slots / steady_*)
   int64_t chain_slots = 0, steady_launches = 0, steady_evals = 0;
   double steady_ms = 0;
-  int cur_live = 0;                // chains in the list the next gradient launch serves
-  void *d_livelog = nullptr;       // [257] live counts logged by rh_compact_kernel, one per tick of a batch (+ the call's first tick)
   int64_t launches = 0;
   // tick engine
   bool tick_engine = false;
   int nsplit = 0, xcd_aware = 1;
   bool compact = true;             // gradient launches and ticks serve the listed (live) chains only
-  void *d_list = nullptr, *d_nlive = nullptr;
-  void *d_qbuf = nullptr, *d_active = nullptr, *d_partial = nullptr, *d_graderr = nullptr;
-  void *d_partial2 = nullptr, *d_rec[2] = {nullptr, nullptr};  // fused launches: the second partial-sum buffer and the two record buffers (alternating)
-  int pp = 0;                                                   // which of the two the next launch writes
+  void *d_qbuf = nullptr, *d_active = nullptr;
+  void *d_rec[2] = {nullptr, nullptr};  // fused launches: the two record buffers (alternating)
   bool fuse = false;  // static HMC on the plain gradient kernel: mid-trajectory updates run as the gradient launch's epilogue
-  std::vector<hipEvent_t> ev;
-  GatherBufs *gb = nullptr;
+  std::vector<Lane> lanes;         // one, or two halves of the chains on two streams (lanes_plan.hpp)
   std::vector<rh_chain_stats_dev> last_stats;
   int64_t grads_at_reset = 0;
 };
@@ -1462,12 +1485,13 @@ int default_nsplit(const rh_model *m, int chains) {
 // workgroups of the slots past the live count -- the last of the grid -- return at once.
 // d_vflag: the chains' request flags (rh_tick_kernel: 2 = gradient only, the log-density of that evaluation is never read) or nullptr.
 void launch_grad(rh_model *m, GatherBufs *gb, void *d_q, void *d_list, void *d_nlive, void *d_vflag, void *d_partial, void *d_graderr, void *d_running,
-                 int chains, int nsplit, int xcd) {
+                 int chains, int nsplit, int xcd, hipStream_t stream = nullptr) {
+  if (!stream) stream = m->stream;
   const int ngroups = (chains + m->grad_k - 1) / m->grad_k;
   if (m->info.gather_mode) {
     void *ga[] = {&m->data, &gb->gd, &d_q, &d_list, &d_nlive, &d_vflag, &d_partial, &d_graderr, &d_running, &chains, &nsplit};
-    if (gb->any_big) launch(m->k_grad_gather, (unsigned)(ngroups * nsplit), 64, m->stream, ga);
-    if (gb->any_small) launch(m->k_grad_gather_scan, (unsigned)(ngroups * nsplit), 64, m->stream, ga);   // (its own row targets: other partial-sum slots)
+    if (gb->any_big) launch(m->k_grad_gather, (unsigned)(ngroups * nsplit), 64, stream, ga);
+    if (gb->any_small) launch(m->k_grad_gather_scan, (unsigned)(ngroups * nsplit), 64, stream, ga);   // (its own row targets: other partial-sum slots)
     return;
   }
   void *args[] = {&m->data, &d_q, &d_list, &d_nlive, &d_vflag, &d_partial, &d_graderr, &d_running, &chains, &nsplit, &xcd};
@@ -1476,9 +1500,9 @@ void launch_grad(rh_model *m, GatherBufs *gb, void *d_q, void *d_list, void *d_n
     const unsigned blocks = (unsigned)(((ctiles + m->glm_w - 1) / m->glm_w) * nsplit);
     const unsigned tile = (unsigned)m->glm_ncols * 66u * (unsigned)sizeof(double);  // the kernel's NBUF rule: two tiles while they fit
     const unsigned lds = (2u * tile + (m->lk_lds ? 6176u : 0u) <= 160u * 1024u ? 2u : 1u) * tile;
-    HIPCHK(hipModuleLaunchKernel(m->k_grad_glm, blocks, 1, 1, 64u * m->glm_w, 1, 1, lds, m->stream, args, nullptr));
+    HIPCHK(hipModuleLaunchKernel(m->k_grad_glm, blocks, 1, 1, 64u * m->glm_w, 1, 1, lds, stream, args, nullptr));
   } else
-    launch(m->k_grad, (unsigned)(ngroups * nsplit), 64, m->stream, args);
+    launch(m->k_grad, (unsigned)(ngroups * nsplit), 64, stream, args);
 }
 }  // namespace
 
@@ -1780,37 +1804,68 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
       nsplit *= subf;
       if (nsplit > 65536) throw Fail{RH_E_INVALID, "grad_splits too large"};
       s->nsplit = nsplit;
-      HIPCHK(hipMalloc(&s->d_list, sizeof(int) * chains));
-      HIPCHK(hipMalloc(&s->d_nlive, sizeof(int)));
-      HIPCHK(hipMalloc(&s->d_livelog, sizeof(int) * 257));
-      HIPCHK(hipMemset(s->d_livelog, 0, sizeof(int) * 257));
-      { std::vector<int> ident((size_t)chains);   // (the list of a sampler that does not compact: every chain, every launch)
-        for (int c = 0; c < chains; c++) ident[(size_t)c] = c;
-        HIPCHK(hipMemcpy(s->d_list, ident.data(), sizeof(int) * chains, hipMemcpyHostToDevice)); }
-      HIPCHK(hipMemset(s->d_nlive, 0, sizeof(int)));
       if (const char *e = rh::knob("RH_XCD_AWARE")) s->xcd_aware = std::atoi(e);
       HIPCHK(hipMalloc(&s->d_qbuf, sizeof(double) * n * chains));
       HIPCHK(hipMalloc(&s->d_active, sizeof(int) * chains));
-      HIPCHK(hipMalloc(&s->d_partial, sizeof(double) * (size_t)m->n_row_targets * nsplit * chains * m->nacc_max));
-      HIPCHK(hipMalloc(&s->d_graderr, sizeof(int)));
       HIPCHK(hipMemset(s->d_qbuf, 0, sizeof(double) * n * chains));
       HIPCHK(hipMemset(s->d_active, 0, sizeof(int) * chains));
-      HIPCHK(hipMemset(s->d_graderr, 0, sizeof(int)));
+      const size_t rec_u64 = (size_t)(3 * n + 8);   // RH_REC_U64 (rh_engine.hip.h)
       {  // The fused launch (rh_grad_fused_kernel: static HMC's mid-trajectory update as the gradient launch's prologue) needs the
          // base sampler-kernel variant (its state layout is compiled into the gradient module), the plain VALU gradient kernel and
          // a lock-step sampler.  Chains are bit-identical with and without it (tests/test_gpu_fused.py); RH_FUSE=0 turns it off.
         bool fuse = m->k_grad_fused && m->k_absorb && s->k_tick == m->k_tick && cfg->sampler == RH_SAMPLER_HMC && !m->k_grad_glm;
         if (const char *e = rh::knob("RH_FUSE")) fuse = fuse && std::atoi(e) != 0;
         if (fuse) {
-          const size_t rec_bytes = sizeof(uint64_t) * (size_t)(3 * n + 8) * chains;   // RH_REC_U64 (rh_engine.hip.h)
-          HIPCHK(hipMalloc(&s->d_partial2, sizeof(double) * (size_t)m->n_row_targets * nsplit * chains * m->nacc_max));
+          const size_t rec_bytes = sizeof(uint64_t) * rec_u64 * chains;
           for (int k = 0; k < 2; k++) { HIPCHK(hipMalloc(&s->d_rec[k], rec_bytes)); HIPCHK(hipMemset(s->d_rec[k], 0, rec_bytes)); }
           s->fuse = true;
         }
       }
-      if (m->info.gather_mode) {
-        HIPCHK(hipMemset(s->d_partial, 0, sizeof(double) * (size_t)m->n_row_targets * nsplit * chains * m->nacc_max));
-        s->gb = new GatherBufs(); s->gb->build(m, chains, nsplit);
+      // The lanes (lanes_plan.hpp): nsplit above came from the total chain count, so a chain's sums are the same in one lane and
+      // in two.  Without a switch lanes_cut's rule decides: two lanes where each alone still offers a wavefront to every SIMD
+      // (measured on cfg 2, profiles/lanes_cfg2: +4 % under static HMC, +1.5..5 % under DefaultConfig).  RH_LANES=1|2 forces the
+      // count (2: wherever there are two chain groups to part).
+      int forced = 0;
+      if (const char *e = rh::knob("RH_LANES")) forced = std::atoi(e) == 1 ? 1 : (std::atoi(e) == 2 ? 2 : 0);
+      const rh_plan::LaneCut cut = rh_plan::lanes_cut(chains, m->k_grad_glm ? 16 : m->grad_k, nsplit, m->k_grad_glm ? m->glm_w : 1,
+                                                      device_cus(m->device), forced);
+      s->lanes.resize((size_t)cut.lanes);
+      const size_t iters_alloc = (size_t)cfg->iterations;   // (a chain's draws are addressed as chain * cfg.iterations * n)
+      for (int li = 0; li < cut.lanes; li++) {
+        Lane &L = s->lanes[(size_t)li];
+        const int f = cut.first[li], lc = cut.count[li];
+        L.first = f; L.chains = lc;
+        if (li == 0) L.stream = m->stream;
+        else { HIPCHK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking)); L.own_stream = true; }
+        HIPCHK(hipEventCreate(&L.e0));
+        HIPCHK(hipEventCreate(&L.e1));
+        L.state = (uint64_t *)s->d_state + (size_t)f * s->state_words;
+        L.seeds = (int64_t *)s->d_seeds + (size_t)2 * f;
+        L.draws = (double *)s->d_draws + (size_t)f * iters_alloc * n;
+        L.stats = (rh_chain_stats_dev *)s->d_stats + f;
+        L.qbuf = (double *)s->d_qbuf + (size_t)f * n;
+        L.active = (int *)s->d_active + f;
+        for (int k = 0; k < 2; k++) L.rec[k] = s->d_rec[k] ? (uint64_t *)s->d_rec[k] + (size_t)f * rec_u64 : nullptr;
+        const size_t partial_bytes = sizeof(double) * (size_t)m->n_row_targets * nsplit * lc * m->nacc_max;
+        HIPCHK(hipMalloc(&L.d_running, sizeof(int)));
+        HIPCHK(hipMalloc(&L.d_list, sizeof(int) * lc));
+        HIPCHK(hipMalloc(&L.d_nlive, sizeof(int)));
+        HIPCHK(hipMalloc(&L.d_livelog, sizeof(int) * 257));
+        HIPCHK(hipMemset(L.d_livelog, 0, sizeof(int) * 257));
+        { std::vector<int> ident((size_t)lc);   // (the list of a sampler that does not compact: every chain, every launch)
+          for (int c = 0; c < lc; c++) ident[(size_t)c] = c;
+          HIPCHK(hipMemcpy(L.d_list, ident.data(), sizeof(int) * lc, hipMemcpyHostToDevice)); }
+        HIPCHK(hipMemset(L.d_nlive, 0, sizeof(int)));
+        HIPCHK(hipMalloc(&L.d_partial, partial_bytes));
+        HIPCHK(hipMalloc(&L.d_graderr, sizeof(int)));
+        HIPCHK(hipMemset(L.d_graderr, 0, sizeof(int)));
+        if (s->fuse) HIPCHK(hipMalloc(&L.d_partial2, partial_bytes));
+        if (m->info.gather_mode) {
+          HIPCHK(hipMemset(L.d_partial, 0, partial_bytes));
+          L.gb = new GatherBufs(); L.gb->build(m, lc, nsplit);
+        }
+        L.livelog.assign(257, 0);
+        L.was_ticked.assign(256, 0);
       }
     }
     // The buffers above were cleared with hipMemset: fill KERNELS on the null stream that return before they have run, while the
@@ -1827,11 +1882,17 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
 extern "C" void rh_sampler_destroy(rh_sampler *s) {
   if (!s) return;
   if (s->m) hipSetDevice(s->m->device);
-  for (void *p : {s->d_state, s->d_seeds, s->d_mass, s->d_draws, s->d_stats, s->d_running, s->d_qbuf, s->d_active, s->d_partial, s->d_graderr, s->d_partial2, s->d_rec[0], s->d_rec[1],
-                  s->d_list, s->d_nlive, s->d_livelog})
+  for (void *p : {s->d_state, s->d_seeds, s->d_mass, s->d_draws, s->d_stats, s->d_running, s->d_qbuf, s->d_active, s->d_rec[0], s->d_rec[1]})
     if (p) hipFree(p);
-  for (hipEvent_t e : s->ev) hipEventDestroy(e);
-  delete s->gb;
+  for (Lane &L : s->lanes) {
+    for (void *p : {L.d_running, L.d_list, L.d_nlive, L.d_livelog, L.d_partial, L.d_partial2, L.d_graderr})
+      if (p) hipFree(p);
+    for (hipEvent_t e : L.ev) hipEventDestroy(e);
+    if (L.e0) hipEventDestroy(L.e0);
+    if (L.e1) hipEventDestroy(L.e1);
+    delete L.gb;
+    if (L.own_stream && L.stream) hipStreamDestroy(L.stream);
+  }
   if (s->e0) hipEventDestroy(s->e0);
   if (s->e1) hipEventDestroy(s->e1);
   delete s;
@@ -1840,109 +1901,164 @@ extern "C" void rh_sampler_destroy(rh_sampler *s) {
 namespace {
 // tick engine: [tick, all chains] [compact] then repeat { [grad] [tick] [compact] } until no chain asks for a gradient any more.
 // rh_compact_kernel lists the chains whose tick asked for a gradient; the gradient launch and the tick behind it serve exactly those.
+// With two lanes every step below is taken for lane 0 and then for lane 1 -- a whole batch is enqueued on one lane's stream before
+// the other's, the device interleaves them -- and a lane whose chains have all arrived drops out of the rounds that follow.
 void advance_to_ticks(rh_sampler *s, int it_stop) {
   rh_model *m = s->m;
   HIPCHK(hipSetDevice(m->device));
-  int chains = s->chains, nsplit = s->nsplit, stop = it_stop, xcd = s->xcd_aware;
-  void *pbuf[2] = {s->d_partial, s->d_partial2};
+  int nsplit = s->nsplit, stop = it_stop, xcd = s->xcd_aware;
   void *no_list = nullptr;
-  void *live_list = s->d_list, *live_n = s->compact ? s->d_nlive : nullptr;   // (without compaction d_list stays the identity)
-  void *vflag = s->d_active;   // gradient-only requests (RH_VALUE_FREE=0: every launch computes the log-density too)
-  if (const char *e = rh::knob("RH_VALUE_FREE")) if (std::atoi(e) == 0) vflag = nullptr;
-  auto tick = [&](int fresh, bool reset_counter, void *partial, bool listed, int log_slot) {
-    if (reset_counter) HIPCHK(hipMemsetAsync(s->d_running, 0, sizeof(int), m->stream));
-    void *lst = listed && s->compact ? live_list : no_list, *nl = listed && s->compact ? live_n : no_list;
+  bool value_free = true;   // gradient-only requests (RH_VALUE_FREE=0: every launch computes the log-density too)
+  if (const char *e = rh::knob("RH_VALUE_FREE")) if (std::atoi(e) == 0) value_free = false;
+  auto tick = [&](Lane &L, int fresh, bool reset_counter, void *partial, bool listed, int log_slot) {
+    int chains = L.chains;
+    if (reset_counter) HIPCHK(hipMemsetAsync(L.d_running, 0, sizeof(int), L.stream));
+    void *lst = listed && s->compact ? L.d_list : no_list, *nl = listed && s->compact ? L.d_nlive : no_list;
     if (m->info.gather_mode) {
-      void *args[] = {&m->data, &s->gb->gd, &s->cfg, &s->d_state, &s->d_seeds, &s->d_mass, &s->d_draws, &s->d_stats, &s->d_running, &s->d_qbuf,
-                      &s->d_active, &partial, &s->d_graderr, &lst, &nl, &chains, &nsplit, &stop, &fresh};
-      launch(s->k_tick, (unsigned)chains, 64, m->stream, args);
+      void *args[] = {&m->data, &L.gb->gd, &s->cfg, &L.state, &L.seeds, &s->d_mass, &L.draws, &L.stats, &L.d_running, &L.qbuf,
+                      &L.active, &partial, &L.d_graderr, &lst, &nl, &chains, &nsplit, &stop, &fresh};
+      launch(s->k_tick, (unsigned)chains, 64, L.stream, args);
     } else {
-      void *args[] = {&m->data, &s->cfg, &s->d_state, &s->d_seeds, &s->d_mass, &s->d_draws, &s->d_stats, &s->d_running, &s->d_qbuf,
-                      &s->d_active, &partial, &s->d_graderr, &lst, &nl, &chains, &nsplit, &stop, &fresh};
-      launch(s->k_tick, (unsigned)chains, 64, m->stream, args);
+      void *args[] = {&m->data, &s->cfg, &L.state, &L.seeds, &s->d_mass, &L.draws, &L.stats, &L.d_running, &L.qbuf,
+                      &L.active, &partial, &L.d_graderr, &lst, &nl, &chains, &nsplit, &stop, &fresh};
+      launch(s->k_tick, (unsigned)chains, 64, L.stream, args);
     }
     if (s->compact) {
-      void *lg = (int *)s->d_livelog + log_slot;
-      void *ca[] = {&s->d_active, &s->d_list, &s->d_nlive, &lg, &chains};
-      launch(m->k_compact, 1u, 1024, m->stream, ca);
+      void *lg = (int *)L.d_livelog + log_slot;
+      void *ca[] = {&L.active, &L.d_list, &L.d_nlive, &lg, &chains};
+      launch(m->k_compact, 1u, 1024, L.stream, ca);
     }
   };
-  auto grad = [&](void *partial) { launch_grad(m, s->gb, s->d_qbuf, live_list, live_n, vflag, partial, s->d_graderr, s->d_running, chains, nsplit, xcd); };
-  // gradient at the point the PREVIOUS launch's gradient moves every chain to (rh_fused_prologue); no tick between the two
-  auto grad_fused = [&](void *partial_in, void *partial_out, void *rec_in, void *rec_out) {
-    void *args[] = {&m->data, &s->d_qbuf, &live_list, &live_n, &partial_in, &partial_out, &s->d_graderr, &s->d_running, &s->d_state, &rec_in, &rec_out,
-                    &chains, &nsplit, &xcd};
-    launch(m->k_grad_fused, (unsigned)(((chains + m->grad_k - 1) / m->grad_k) * nsplit), 64, m->stream, args);
+  auto grad = [&](Lane &L, void *partial) {
+    launch_grad(m, L.gb, L.qbuf, L.d_list, s->compact ? L.d_nlive : nullptr /* (without compaction d_list stays the identity) */,
+                value_free ? L.active : nullptr, partial, L.d_graderr, L.d_running, L.chains, nsplit, xcd, L.stream);
   };
-  auto absorb = [&](void *rec) {
-    void *args[] = {&s->d_state, &rec, &s->d_qbuf, &s->d_active, &chains};
-    launch(m->k_absorb, (unsigned)chains, 64, m->stream, args);
+  // gradient at the point the PREVIOUS launch's gradient moves every chain to (rh_fused_prologue); no tick between the two
+  auto grad_fused = [&](Lane &L, void *partial_in, void *partial_out, void *rec_in, void *rec_out) {
+    int chains = L.chains;
+    void *live_n = s->compact ? L.d_nlive : nullptr;
+    void *args[] = {&m->data, &L.qbuf, &L.d_list, &live_n, &partial_in, &partial_out, &L.d_graderr, &L.d_running, &L.state, &rec_in, &rec_out,
+                    &chains, &nsplit, &xcd};
+    launch(m->k_grad_fused, (unsigned)(((chains + m->grad_k - 1) / m->grad_k) * nsplit), 64, L.stream, args);
+  };
+  auto absorb = [&](Lane &L, void *rec) {
+    int chains = L.chains;
+    void *args[] = {&L.state, &rec, &L.qbuf, &L.active, &chains};
+    launch(m->k_absorb, (unsigned)chains, 64, L.stream, args);
   };
   // Static HMC in the sampling phase runs in lock step: every chain was paused at the head of the same iteration, so gradient
   // request j of a trajectory is request j of every chain, and all but the L-th are followed by the plain update the fused
   // launch that follows performs itself in its prologue.  (A chain that is out of step anyway is simply served by the next tick.)
-  const int L = std::max(1, s->cfg.hmc_steps);
-  const bool fuse_now = s->fuse && s->warmed && s->cfg.sampler == RH_SAMPLER_HMC && L > 1;
-  long long pos = 0;  // gradient launches since the first tick of this call
+  const int Ltraj = std::max(1, s->cfg.hmc_steps);
+  const bool fuse_now = s->fuse && s->warmed && s->cfg.sampler == RH_SAMPLER_HMC && Ltraj > 1;
   // batch size between host checks: exact for static HMC in the sampling phase, otherwise 32 ticks
   int remaining_hint = 32;
   if (s->cfg.sampler == RH_SAMPLER_HMC && s->warmed) {
     const int iters = it_stop - (s->cfg.warmup + s->it_done);
     remaining_hint = std::max(1, iters * std::max(1, s->cfg.hmc_steps));
   }
-  HIPCHK(hipEventRecord(s->e0, m->stream));
-  tick(s->started ? 0 : 1, true, s->d_partial, false, 256);
+  // the union of the live lanes' [e0, e1] spans of this round -> total_ms
+  auto add_total = [&]() {
+    hipEvent_t ref = nullptr;
+    double t0[2], t1[2], share[2];
+    int k = 0;
+    for (Lane &L : s->lanes) {
+      if (!L.live) continue;
+      float a = 0, b = 0;
+      if (!ref) ref = L.e0; else HIPCHK(hipEventElapsedTime(&a, ref, L.e0));
+      HIPCHK(hipEventElapsedTime(&b, L.e0, L.e1));
+      t0[k] = a; t1[k] = (double)a + b; k++;
+    }
+    s->total_ms += k == 1 ? t1[0] - t0[0] : rh_plan::busy_shares(k, t0, t1, share);
+  };
+  for (Lane &L : s->lanes) {
+    L.live = true; L.pos = 0; L.remaining_hint = remaining_hint;
+    HIPCHK(hipEventRecord(L.e0, L.stream));
+    tick(L, s->started ? 0 : 1, true, L.d_partial, false, 256);
+    HIPCHK(hipEventRecord(L.e1, L.stream));
+  }
   s->started = true;
-  HIPCHK(hipEventRecord(s->e1, m->stream));
-  std::vector<int> livelog(257, 0);
-  std::vector<char> was_ticked(256, 0);
+  std::vector<double> t0, t1, share;
   for (bool first = true;; first = false) {
-    int running = 0;
-    HIPCHK(hipMemcpyAsync(&running, s->d_running, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    if (first && s->compact) HIPCHK(hipMemcpyAsync(&s->cur_live, (int *)s->d_livelog + 256, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    if (!s->compact) s->cur_live = chains;
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, s->e0, s->e1));
-    s->total_ms += ms;
-    if (running == 0) break;
-    const int B = std::min(remaining_hint, 256);
-    while ((int)s->ev.size() < 2 * B) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); s->ev.push_back(e); }
-    HIPCHK(hipEventRecord(s->e0, m->stream));
-    bool pending = false, prev_rec = false;   // the previous launch's gradient has not been consumed by a tick / it left records
-    for (int i = 0; i < B; i++) {
-      // the last launch of a batch is always followed by a tick: it is the tick that counts the chains still running
-      const bool ticked = !(fuse_now && (int)(pos % L) + 1 < L && i != B - 1);
-      const int cur = fuse_now ? s->pp : 0;
-      HIPCHK(hipEventRecord(s->ev[2 * i], m->stream));
-      if (pending) grad_fused(pbuf[cur ^ 1], pbuf[cur], prev_rec ? s->d_rec[cur ^ 1] : nullptr, s->d_rec[cur]);
-      else grad(pbuf[cur]);
-      HIPCHK(hipEventRecord(s->ev[2 * i + 1], m->stream));
-      prev_rec = pending;
-      if (ticked) {
-        if (prev_rec) absorb(s->d_rec[cur]);
-        tick(0, false, pbuf[cur], true, i);
+    for (Lane &L : s->lanes) {
+      if (!L.live) continue;
+      L.running = 0;
+      HIPCHK(hipMemcpyAsync(&L.running, L.d_running, sizeof(int), hipMemcpyDeviceToHost, L.stream));
+      if (first && s->compact) HIPCHK(hipMemcpyAsync(&L.cur_live, (int *)L.d_livelog + 256, sizeof(int), hipMemcpyDeviceToHost, L.stream));
+    }
+    for (Lane &L : s->lanes) if (L.live) HIPCHK(hipStreamSynchronize(L.stream));
+    add_total();
+    int nlive_lanes = 0;
+    for (Lane &L : s->lanes) {
+      if (!L.live) continue;
+      if (!s->compact) L.cur_live = L.chains;
+      if (L.running == 0) L.live = false; else nlive_lanes++;
+    }
+    if (nlive_lanes == 0) break;
+    for (Lane &L : s->lanes) {
+      if (!L.live) continue;
+      void *pbuf[2] = {L.d_partial, L.d_partial2};
+      const int B = L.B = std::min(L.remaining_hint, 256);
+      while ((int)L.ev.size() < 2 * B) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); L.ev.push_back(e); }
+      HIPCHK(hipEventRecord(L.e0, L.stream));
+      bool pending = false, prev_rec = false;   // the previous launch's gradient has not been consumed by a tick / it left records
+      for (int i = 0; i < B; i++) {
+        // the last launch of a batch is always followed by a tick: it is the tick that counts the chains still running
+        const bool ticked = !(fuse_now && (int)(L.pos % Ltraj) + 1 < Ltraj && i != B - 1);
+        const int cur = fuse_now ? L.pp : 0;
+        HIPCHK(hipEventRecord(L.ev[2 * i], L.stream));
+        if (pending) grad_fused(L, pbuf[cur ^ 1], pbuf[cur], prev_rec ? L.rec[cur ^ 1] : nullptr, L.rec[cur]);
+        else grad(L, pbuf[cur]);
+        HIPCHK(hipEventRecord(L.ev[2 * i + 1], L.stream));
+        prev_rec = pending;
+        if (ticked) {
+          if (prev_rec) absorb(L, L.rec[cur]);
+          tick(L, 0, false, pbuf[cur], true, i);
+        }
+        pending = !ticked;
+        L.was_ticked[(size_t)i] = ticked ? 1 : 0;
+        if (fuse_now) L.pp ^= 1;
+        L.pos++;
       }
-      pending = !ticked;
-      was_ticked[(size_t)i] = ticked ? 1 : 0;
-      if (fuse_now) s->pp ^= 1;
-      pos++;
+      HIPCHK(hipEventRecord(L.e1, L.stream));
     }
-    HIPCHK(hipEventRecord(s->e1, m->stream));
-    if (s->compact) HIPCHK(hipMemcpyAsync(livelog.data(), s->d_livelog, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    for (int i = 0; i < B; i++) {
-      float g = 0;
-      HIPCHK(hipEventElapsedTime(&g, s->ev[2 * i], s->ev[2 * i + 1]));
-      s->kernel_ms += g;
-      // launch i served the chains listed by the last compaction before it
-      const int served = s->cur_live;
-      s->chain_slots += served;
-      if ((int64_t)served * 10 >= (int64_t)chains * 9) { s->steady_ms += g; s->steady_launches += 1; s->steady_evals += served; }
-      if (s->compact && was_ticked[(size_t)i]) s->cur_live = livelog[(size_t)i];
+    // (a copy to pageable host memory returns when it is done: the read-backs come after BOTH lanes' batches have been enqueued)
+    for (Lane &L : s->lanes)
+      if (L.live && s->compact) HIPCHK(hipMemcpyAsync(L.livelog.data(), L.d_livelog, sizeof(int) * (size_t)L.B, hipMemcpyDeviceToHost, L.stream));
+    for (Lane &L : s->lanes) if (L.live) HIPCHK(hipStreamSynchronize(L.stream));
+    // Every launch's span; with two lanes in flight on one time base (hipEventElapsedTime from one reference event works across
+    // the streams of a device), and a launch is charged its busy share: the time it ran alone + half of the time it ran beside the
+    // other lane's.  kernel_ms then is the time during which a gradient launch was running, and never exceeds total_ms.
+    t0.clear(); t1.clear();
+    hipEvent_t ref = nullptr;
+    for (Lane &L : s->lanes) {
+      if (!L.live) continue;
+      if (!ref && nlive_lanes > 1) ref = L.e0;
+      for (int i = 0; i < L.B; i++) {
+        float a = 0, g = 0;
+        if (ref) HIPCHK(hipEventElapsedTime(&a, ref, L.ev[2 * i]));
+        HIPCHK(hipEventElapsedTime(&g, L.ev[2 * i], L.ev[2 * i + 1]));
+        t0.push_back(a); t1.push_back((double)a + g);
+      }
     }
-    s->launches += B;
-    remaining_hint = std::max(32, remaining_hint - B);
+    share.resize(t0.size());
+    if (nlive_lanes > 1) rh_plan::busy_shares((int)t0.size(), t0.data(), t1.data(), share.data());
+    else for (size_t i = 0; i < t0.size(); i++) share[i] = t1[i] - t0[i];
+    size_t at = 0;
+    for (Lane &L : s->lanes) {
+      if (!L.live) continue;
+      for (int i = 0; i < L.B; i++, at++) {
+        const double g = share[at];
+        s->kernel_ms += g;
+        // launch i served the chains listed by the last compaction before it
+        const int served = L.cur_live;
+        s->chain_slots += served;
+        if ((int64_t)served * 10 >= (int64_t)L.chains * 9) { s->steady_ms += g; s->steady_launches += 1; s->steady_evals += served; }
+        if (s->compact && L.was_ticked[(size_t)i]) L.cur_live = L.livelog[(size_t)i];
+      }
+      s->launches += L.B;
+      L.remaining_hint = std::max(32, L.remaining_hint - L.B);
+    }
   }
 }
 

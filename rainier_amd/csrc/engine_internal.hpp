@@ -52,6 +52,12 @@ inline std::string device_arch(int dev) {
   const std::string arch = prop.gcnArchName;
   return arch.substr(0, arch.find(':'));
 }
+// compute units of a device (4 SIMDs each)
+inline int device_cus(int dev) {
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  return cus;
+}
 // -1: the current device; makes the device current and returns its ordinal
 inline int use_device(int device, const char *fn) {
   int ndev = 0;
