@@ -40,7 +40,7 @@ extern "C" {
                              5: rh_model_engines, rh_compile_count;
                              6: rh_timing.chain_slots / steady_* (the tick engine's gradient launches serve the live chains only);
                                 (still 6, additions only: rh_sampler_diagnostics, rh_diagnostics_device, rh_predict_*, rh_*_summary*, rh_generate_*,
-                                 rh_sampler_generate) */
+                                 rh_sampler_generate, rh_sampler_covariance, rh_covariance_device, rh_covariance_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -413,6 +413,40 @@ int rh_sampler_generate(rh_sampler *s, rh_predict *p, rh_generate *g, int32_t fi
 /* No device needed: the sampling kernel's code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a launch
  * (the generators of core/Continuous.scala:54-215 and core/Discrete.scala:38-186 above); *code_out is malloc'ed, freed with rh_free. */
 int rh_generate_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- posterior covariance and correlation over device-resident draws --------------------------------------------------------
+ * How two parameters move together: the reference's notebooks plot pairs (rainier-notebook package.scala:79-98); this is the pooled
+ * sample covariance of the kept draws with the divisor of CovarianceEstimator.covariance (MassMatrixEstimator.scala:38-47), and
+ * optionally the correlation, computed where the draws are (csrc/device/rh_cov.hip.h: X^T X of the centred draws on the fp64
+ * matrix cores).  Window, thinning and flat rows are rh_sampler_summary's: kept = ceil(count/thin), N = chains * kept, flat row
+ * r = c * kept + j is draw (c, first + j*thin).  Column k of the result is parameter cols[k] (duplicates allowed); cols == NULL:
+ * all nvars in order, and ncols must be 0 or nvars.  K = ncols, or nvars without a list.
+ * The sums run in a fixed order that depends on N alone.  A split is 4096 consecutive flat rows, S = ceil(N/4096):
+ *   mean[k]    = (sum over s ascending of (sum over the rows r of split s ascending of x[r][k])) / (double)N, every sum one
+ *                accumulator from +0.0 with plain adds;
+ *   d[r][k]    = x[r][k] - mean[k], one rounding (two passes: a mean many standard deviations from zero costs no digits);
+ *   P_s[a][b]  = one accumulator from +0.0, r ascending in split s: acc = fma(d[r][a], d[r][b], acc);
+ *   cov[a][b]  = (sum over s ascending of P_s[a][b]) / (double)(N - 1), bitwise symmetric;
+ *   corr[a][b] = cov[a][b] / (sqrt(cov[a][a]) * sqrt(cov[b][b])), IEEE operations in that order; the diagonal is exactly 1.0 where
+ *                cov[a][a] is finite and > 0, else NaN, and so is an entry whose two columns are one parameter (a list that names
+ *                it twice); not clamped, so |corr| may exceed 1 by rounding.
+ * A NaN in a column makes that row and column NaN and touches nothing else.  Nothing depends on tiling, chunking, the order of the
+ * column list or the launch: entry (a, b) of a call over cols has the bits of entry (cols[a], cols[b]) of the call over all columns.
+ * mean [K], cov [K][K], corr [K][K]: caller-allocated on the host; each may be NULL, not all three.
+ * The partial sums live in a bounded device workspace (128 MiB, walked in chunks of tile pairs of 64 x 64 columns); a shape whose
+ * single tile pair is beyond it (S * 32 KiB) returns RH_E_UNSUPPORTED before any launch.  A broken window, N < 2, an index outside
+ * [0, nvars), ncols < 1 with a list: RH_E_INVALID.  No device: RH_E_DEVICE (no CPU fallback).
+ * The sampler form goes to the sampler's stream behind its pending work, is not part of rh_timing and does not alter the chains;
+ * count <= iterations completed - first. */
+int rh_sampler_covariance(rh_sampler *s, int32_t first, int32_t count, int32_t thin, const int32_t *cols, int32_t ncols,
+                          double *mean, double *cov, double *corr);
+/* the same over any device buffer [chains][iterations][nvars] on `device` (-1: the current one), e.g. a predictor's *dev_out or
+ * rh_comm_allgather_draws' *dev_out; synchronises the device before and after */
+int rh_covariance_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                         int32_t count, int32_t thin, const int32_t *cols, int32_t ncols, double *mean, double *cov, double *corr);
+/* No device needed: the covariance kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_covariance_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */

@@ -5,8 +5,9 @@
   frontend.py      small expression DSL that writes RIR (stands in for the JVM front-end in tests/bench)
   models.py        the BASELINE.json configurations as RIR + synthetic data
 """
-from .sampler import (DefaultConfig, DenseMassMatrixTuner, DensityFunction, DiagonalMassMatrix, DiagonalMassMatrixTuner,  # noqa: F401
+from .sampler import (Covariance, DefaultConfig, DenseMassMatrixTuner, DensityFunction, DiagonalMassMatrix,  # noqa: F401
+                      DiagonalMassMatrixTuner,
                       DualAvgTuner, EHMC, EHMCSampler, Generator, HMC, HMCSampler, IdentityMassMatrixTuner, Model, NUTSSampler, Predictor,
-                      RainierHipError, Sampler, SamplerConfig, StaticMassMatrix, StaticStepSize, Summary, Trace,
+                      RainierHipError, Sampler, SamplerConfig, StaticMassMatrix, StaticStepSize, Summary, Trace, covariance_device,
                       diagnostics, diagnostics_device, format_precis, gen, generate_device, make_config, predict, predict_device, sample_multi,
                       summary_device)

@@ -36,6 +36,8 @@ EXPORTS = [
     "rh_sampler_summary", "rh_summary_device",
     # Trace.predict of a Distribution over device-resident draws (core/Trace.scala:34-41, core/Generator.scala:171-174)
     "rh_generate_create", "rh_generate_destroy", "rh_generate_nout", "rh_generate_device", "rh_sampler_generate", "rh_generate_lower_only",
+    # covariance / correlation over device-resident draws (rainier-notebook package.scala:79-98, MassMatrixEstimator.scala:38-47)
+    "rh_sampler_covariance", "rh_covariance_device", "rh_covariance_lower_only",
 ]
 GEN_REAL, GEN_NORMAL, GEN_CAUCHY, GEN_LAPLACE, GEN_UNIFORM, GEN_LOGNORMAL, GEN_GAMMA, GEN_BETA, GEN_BERNOULLI, GEN_GEOMETRIC, GEN_POISSON = range(11)
 GEN_F_DOMAIN, GEN_F_CAP = 1, 2
@@ -145,6 +147,10 @@ def lib():
     L.rh_generate_device.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, dp, C.POINTER(vp), C.POINTER(C.c_int32)]
     L.rh_sampler_generate.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, dp, C.POINTER(vp), C.POINTER(C.c_int32)]
     L.rh_generate_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    ip = C.POINTER(C.c_int32)
+    L.rh_sampler_covariance.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, dp, dp, dp]
+    L.rh_covariance_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, dp, dp, dp]
+    L.rh_covariance_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_comm_unique_id.argtypes = [C.c_char_p]
     L.rh_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.rh_comm_destroy.argtypes = [vp]
@@ -305,6 +311,18 @@ def generate_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_generate_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def covariance_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_cov.hip.h (covariance / correlation on the device: X^T X of the centred draws on the fp64 matrix cores) -> code
+    object for `arch`, without a device: compiled through the kernel cache and judged as before a launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_covariance_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

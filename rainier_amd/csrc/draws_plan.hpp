@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -10,8 +10,10 @@
 // the constants are the device headers' own: their block routines compile as plain C++ in host mode
 #define RH_TRACE_HOST 1
 #define RH_SUMMARY_HOST 1
+#define RH_COV_HOST 1
 #include "device/rh_trace.hip.h"
 #include "device/rh_summary.hip.h"
+#include "device/rh_cov.hip.h"
 // rh_generate.hip.h's routine needs the prelude's rng around it: the CPU test's driver defines RH_GENERATE_HOST with one in place
 #ifndef RH_GENERATE_HOST
 #define RG_CONSTANTS_ONLY 1
@@ -50,6 +52,26 @@ inline Summary summary_plan(long long chains, long long count, long long thin, l
   while (P.run(P.passes) < P.N) P.passes++;
   for (int k = 0; k < nprobs; k++) P.idx[k] = std::min<long long>(P.N - 1, (long long)std::floor((double)P.N * probs[k]));
   if (hdpi_prob > 0.0) P.hidx = std::max<long long>(1, std::min<long long>(P.N, (long long)std::ceil(hdpi_prob * (double)P.N)));
+  return P;
+}
+// ---- covariance / correlation (device/rh_cov.hip.h) ----
+struct Covariance {
+  long long kept, N, S;          // kept iterations per chain; flat rows; splits of RC_SPLIT rows
+  long long ctiles, pairs;       // column tiles of RC_TC; tile pairs bi <= bj, in rc_pair_of's order
+  long long per_pair, pc;        // workspace bytes of one tile pair (its S partial tiles); tile pairs per chunk
+  bool over_cap;                 // one tile pair alone is beyond the cap
+};
+// K: the selected columns; cap: RC_WS_CAP_BYTES (a parameter for the CPU tests' driver, where small shapes make several chunks)
+inline Covariance covariance_plan(long long chains, long long count, long long thin, long long K, long long cap = RC_WS_CAP_BYTES) {
+  Covariance P = {};
+  P.kept = (count + thin - 1) / thin;
+  P.N = chains * P.kept;
+  P.S = (P.N + RC_SPLIT - 1) / RC_SPLIT;
+  P.ctiles = (K + RC_TC - 1) / RC_TC;
+  P.pairs = P.ctiles * (P.ctiles + 1) / 2;
+  P.per_pair = RC_PAIR_BYTES(P.S);
+  P.over_cap = P.per_pair > cap;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, P.pairs));
   return P;
 }
 // ---- predict (device/rh_predict.hip.h) ----

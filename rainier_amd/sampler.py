@@ -434,6 +434,38 @@ def summary_device(ptr: int, chains: int, iterations: int, nvars: int, device: i
     return _summary_result(call, int(nvars), probs, hdpi)
 
 
+class Covariance(NamedTuple):
+    """How the parameters move together: mean [K], cov [K][K] (the pooled sample covariance of the kept draws, divisor N - 1 as in
+    MassMatrixEstimator.scala:38-47), corr [K][K] (None when not asked for; the diagonal is 1.0, or NaN for a column without
+    variance) and the columns they are about (parameter cols[k] is row and column k)."""
+    mean: np.ndarray
+    cov: np.ndarray
+    corr: Optional[np.ndarray]
+    cols: Tuple[int, ...]
+
+
+def _covariance_result(call, nvars, cols, corr, model=None):
+    """shared by Sampler.covariance and covariance_device: call(cols, ncols, mean, cov, corr) -> rc"""
+    sel = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+    k = int(nvars) if sel is None else len(sel)
+    mean, cov, cr = np.zeros(k), np.zeros((k, k)), np.zeros((k, k)) if corr else None
+    buf = sel if sel is None or k else np.zeros(1, dtype=np.int32)       # an empty list is a list (refused), not "all columns"
+    _capi.check(call(buf.ctypes.data_as(C.POINTER(C.c_int32)) if sel is not None else None, k if sel is not None else 0, _capi.dptr(mean),
+                     _capi.dptr(cov), _capi.dptr(cr) if corr else None), model)
+    return Covariance(mean, cov, cr, tuple(range(k)) if sel is None else tuple(sel.tolist()))
+
+
+def covariance_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
+                      thin: int = 1, cols: Optional[Sequence[int]] = None, corr: bool = False) -> Covariance:
+    """The pooled sample covariance (and, with corr = True, the correlation) of the kept iterations first + j * thin over a device
+    buffer [chains][iterations][nvars] (a sampler's draws, a predictor's to_host = False result, Comm.allgather_draws(to_host=False)),
+    computed where the draws are (rh_covariance_device); cols: the parameters asked for, in the result's order (None: all)."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_covariance_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count,
+                                                       int(thin), *a)
+    return _covariance_result(call, nvars, cols, corr)
+
+
 def format_precis(names: Sequence[str], summary: Summary) -> str:
     """precis' table (rainier-notebook package.scala:393-417, without the correlations) as a string: Mean, StdDev and the first two
     order statistics of `summary`, %10.2f, one line per parameter."""
@@ -534,6 +566,15 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_summary(self._h, int(first), count, int(thin), *a)
         return _summary_result(call, self.model.nVars, probs, hdpi, self.model._h)
+
+    def covariance(self, first: int = 0, count: Optional[int] = None, thin: int = 1, cols: Optional[Sequence[int]] = None,
+                   corr: bool = False) -> Covariance:
+        """The pooled sample covariance (and, with corr = True, the correlation) of the parameters over the kept iterations
+        first + j * thin of all chains, computed where the draws are (rh_sampler_covariance); cols: the parameters asked for, in the
+        result's order (None: all); count = None: everything completed so far.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_covariance(self._h, int(first), count, int(thin), *a)
+        return _covariance_result(call, self.model.nVars, cols, corr, self.model._h)
 
     def mass_dense(self) -> np.ndarray:
         """DenseMassMatrix.elements of every chain: [chains][nVars][nVars] (DenseMassMatrixTuner only)."""
