@@ -40,7 +40,8 @@ extern "C" {
                              5: rh_model_engines, rh_compile_count;
                              6: rh_timing.chain_slots / steady_* (the tick engine's gradient launches serve the live chains only);
                                 (still 6, additions only: rh_sampler_diagnostics, rh_diagnostics_device, rh_predict_*, rh_*_summary*, rh_generate_*,
-                                 rh_sampler_generate, rh_sampler_covariance, rh_covariance_device, rh_covariance_lower_only) */
+                                 rh_sampler_generate, rh_sampler_covariance, rh_covariance_device, rh_covariance_lower_only,
+                                 rh_sampler_histogram, rh_histogram_device, rh_sampler_histogram2d, rh_histogram2d_device, rh_histogram_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -447,6 +448,51 @@ int rh_covariance_device(const void *dev_draws, int32_t device, int32_t chains, 
 /* No device needed: the covariance kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_covariance_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- posterior histograms and joint count grids over device-resident draws ----------------------------------------------------
+ * The shape of a posterior: the reference's density(seq, bounds) -- a histogram of one parameter's pooled draws between doubles.min
+ * and doubles.max or between given bounds -- and scatter / contour of a pair (rainier-notebook package.scala:63-98), computed where
+ * the draws are (csrc/device/rh_hist.hip.h: one binning pass, LDS integer adds); only the counts come back.  Window, thinning and
+ * flat rows are rh_sampler_summary's: kept = ceil(count/thin), N = chains * kept, flat row r = c * kept + j is draw
+ * (c, first + j*thin).  Column k of the result is parameter cols[k] (duplicates allowed); cols == NULL: all nvars in order, and ncols
+ * must be 0 or nvars.  K = ncols, or nvars without a list.  1 <= nbins <= 1024.
+ * Bounds: range is [K][2] on the host or NULL.  Column k takes (lo, hi) = range[k] unless range is NULL or both entries are NaN; then
+ * lo and hi are the smallest and largest FINITE value of the pooled column, found on the device (2K doubles return; a -0.0 extreme
+ * is returned as +0.0; a column with no finite value gets NaN edges, zero counts in every bin, and its rows land in under / over /
+ * nan).  lo == hi, given or automatic: lo -= 0.5, hi += 0.5 (numpy's rule).  Where that changes nothing (a constant of magnitude 2^53 or
+ * more) the width stays 0: all edges are equal and every row counts in the last, closed bin.  Given bounds must be finite with lo <= hi and hi - lo
+ * finite, else RH_E_INVALID.
+ * Edges: built on the host in double and returned.  With w = hi - lo: e[0] = lo, e[i] = min(hi, max(e[i-1], lo + ((double)i * w) /
+ * (double)nbins)) for 0 < i < nbins, e[nbins] = hi: non-decreasing; they may repeat where w is a few ulps of lo.
+ * Counts are defined against the returned edges and by nothing else (IEEE comparisons): counts[k][b] is the number of rows with
+ * e[b] <= x < e[b+1] for b < nbins-1; the last bin is closed, e[nbins-1] <= x <= e[nbins]; under[k]: x < e[0] (-inf too); over[k]:
+ * x > e[nbins] (+inf too); nan[k]: the NaNs; sum(counts[k]) + under[k] + over[k] + nan[k] == N.  That is np.histogram(finite values,
+ * bins = e).  Nothing depends on tiling, chunking, the order of the column list or the launch: entry k of a call over cols equals
+ * entry cols[k] of the call over all columns given the same bounds.
+ * edges [K][nbins+1], counts [K][nbins] (int64), under / over / nan [K] (each may be NULL): caller-allocated on the host.
+ * The partial counts live in a bounded device workspace (128 MiB, walked in chunks of column tiles); a shape whose single tile is
+ * beyond it returns RH_E_UNSUPPORTED before any launch.  A broken window, N < 1, an index outside [0, nvars), nbins out of range, bad
+ * bounds, ncols < 1 with a list: RH_E_INVALID, the message names the argument.  No device: RH_E_DEVICE (no CPU fallback).
+ * The sampler form goes to the sampler's stream behind its pending work, is not part of rh_timing and does not alter the chains. */
+int rh_sampler_histogram(rh_sampler *s, int32_t first, int32_t count, int32_t thin, const int32_t *cols, int32_t ncols, int32_t nbins,
+                         const double *range, double *edges, int64_t *counts, int64_t *under, int64_t *over, int64_t *nan);
+/* the same over any device buffer [chains][iterations][nvars] on `device` (-1: the current one); synchronises the device before and after */
+int rh_histogram_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                        int32_t count, int32_t thin, const int32_t *cols, int32_t ncols, int32_t nbins, const double *range,
+                        double *edges, int64_t *counts, int64_t *under, int64_t *over, int64_t *nan);
+/* Pairs: pairs is [npairs][2] parameter indices (npairs >= 1, a == b allowed); nbx, nby >= 1 with nbx * nby <= 4096; range is
+ * [npairs][2][2] ((lo, hi) of x, then of y) or NULL, with the rules above per axis and the edge formula per axis.  grid[p][bx][by]
+ * counts the rows whose x falls in bin bx of xedges[p] and whose y falls in bin by of yedges[p]; outside[p] (may be NULL) the rows where
+ * either coordinate is out of range or NaN; sum(grid[p]) + outside[p] == N.  That is np.histogram2d(x, y, bins = [xedges, yedges]).
+ * xedges [npairs][nbx+1], yedges [npairs][nby+1], grid [npairs][nbx][nby] (int64), outside [npairs]. */
+int rh_sampler_histogram2d(rh_sampler *s, int32_t first, int32_t count, int32_t thin, const int32_t *pairs, int32_t npairs, int32_t nbx,
+                           int32_t nby, const double *range, double *xedges, double *yedges, int64_t *grid, int64_t *outside);
+int rh_histogram2d_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                          int32_t count, int32_t thin, const int32_t *pairs, int32_t npairs, int32_t nbx, int32_t nby,
+                          const double *range, double *xedges, double *yedges, int64_t *grid, int64_t *outside);
+/* No device needed: the histogram kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_histogram_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */

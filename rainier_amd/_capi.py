@@ -38,7 +38,11 @@ EXPORTS = [
     "rh_generate_create", "rh_generate_destroy", "rh_generate_nout", "rh_generate_device", "rh_sampler_generate", "rh_generate_lower_only",
     # covariance / correlation over device-resident draws (rainier-notebook package.scala:79-98, MassMatrixEstimator.scala:38-47)
     "rh_sampler_covariance", "rh_covariance_device", "rh_covariance_lower_only",
+    # histograms / joint count grids over device-resident draws (rainier-notebook package.scala:63-98)
+    "rh_sampler_histogram", "rh_histogram_device", "rh_histogram_lower_only",
 ]
+# ... and the two whose names hold a digit, which that test's pattern of a declaration does not read (tests/test_histogram_device_cpu.py checks them)
+EXPORTS_2D = ["rh_sampler_histogram2d", "rh_histogram2d_device"]
 GEN_REAL, GEN_NORMAL, GEN_CAUCHY, GEN_LAPLACE, GEN_UNIFORM, GEN_LOGNORMAL, GEN_GAMMA, GEN_BETA, GEN_BERNOULLI, GEN_GEOMETRIC, GEN_POISSON = range(11)
 GEN_F_DOMAIN, GEN_F_CAP = 1, 2
 
@@ -151,6 +155,12 @@ def lib():
     L.rh_sampler_covariance.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, dp, dp, dp]
     L.rh_covariance_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, dp, dp, dp]
     L.rh_covariance_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    lp, i32 = C.POINTER(C.c_int64), C.c_int32
+    L.rh_sampler_histogram.argtypes = [vp, i32, i32, i32, ip, i32, i32, dp, dp, lp, lp, lp, lp]
+    L.rh_histogram_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ip, i32, i32, dp, dp, lp, lp, lp, lp]
+    L.rh_sampler_histogram2d.argtypes = [vp, i32, i32, i32, ip, i32, i32, i32, dp, dp, dp, lp, lp]
+    L.rh_histogram2d_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ip, i32, i32, i32, dp, dp, dp, lp, lp]
+    L.rh_histogram_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_comm_unique_id.argtypes = [C.c_char_p]
     L.rh_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.rh_comm_destroy.argtypes = [vp]
@@ -323,6 +333,18 @@ def covariance_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_covariance_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def histogram_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_hist.hip.h (histograms and joint count grids on the device: one binning pass with LDS integer adds) -> code
+    object for `arch`, without a device: compiled through the kernel cache and judged as before a launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_histogram_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -11,9 +11,11 @@
 #define RH_TRACE_HOST 1
 #define RH_SUMMARY_HOST 1
 #define RH_COV_HOST 1
+#define RH_HIST_HOST 1
 #include "device/rh_trace.hip.h"
 #include "device/rh_summary.hip.h"
 #include "device/rh_cov.hip.h"
+#include "device/rh_hist.hip.h"
 // rh_generate.hip.h's routine needs the prelude's rng around it: the CPU test's driver defines RH_GENERATE_HOST with one in place
 #ifndef RH_GENERATE_HOST
 #define RG_CONSTANTS_ONLY 1
@@ -73,6 +75,63 @@ inline Covariance covariance_plan(long long chains, long long count, long long t
   P.over_cap = P.per_pair > cap;
   P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, P.pairs));
   return P;
+}
+// ---- histograms and joint count grids (device/rh_hist.hip.h) ----
+struct Histogram {
+  long long kept, N, S;          // kept iterations per chain; flat rows; splits of RHH_SPLIT rows
+  long long cpt, tiles, mtiles;  // columns of a tile at this nbins (rhh_tile_cols); tiles of the binning pass; tiles of RHH_TC of the min / max pass
+  long long lds_bytes;           // the binning launch's dynamic LDS
+  long long per_tile, tc;        // workspace bytes of one tile (its S partial histograms); tiles per chunk
+  bool over_cap;                 // one tile alone is beyond the cap
+};
+// K: the selected columns; cap: RHH_WS_CAP_BYTES (a parameter for the CPU tests' driver, where small shapes make several chunks)
+inline Histogram histogram_plan(long long chains, long long count, long long thin, long long K, int nbins, long long cap = RHH_WS_CAP_BYTES) {
+  Histogram P = {};
+  P.kept = (count + thin - 1) / thin;
+  P.N = chains * P.kept;
+  P.S = (P.N + RHH_SPLIT - 1) / RHH_SPLIT;
+  P.cpt = rhh_tile_cols(nbins);
+  P.tiles = (K + P.cpt - 1) / P.cpt;
+  P.mtiles = (K + RHH_TC - 1) / RHH_TC;
+  P.lds_bytes = P.cpt * RHH_COL_BYTES(nbins);
+  P.per_tile = P.S * P.cpt * (nbins + RHH_TALLIES) * 4;
+  P.over_cap = P.per_tile > cap;
+  P.tc = std::max<long long>(1, std::min<long long>(cap / P.per_tile, P.tiles));
+  return P;
+}
+struct Histogram2d {
+  long long kept, N, S;          // as above
+  long long words, lds_bytes;    // u32 words of one partial (nbx * nby cells and the rows outside); the pair launch's dynamic LDS
+  long long per_pair, pc;        // workspace bytes of one pair; pairs per chunk
+  bool over_cap;
+};
+inline Histogram2d histogram2d_plan(long long chains, long long count, long long thin, long long npairs, int nbx, int nby, long long cap = RHH_WS_CAP_BYTES) {
+  Histogram2d P = {};
+  P.kept = (count + thin - 1) / thin;
+  P.N = chains * P.kept;
+  P.S = (P.N + RHH_SPLIT - 1) / RHH_SPLIT;
+  P.words = RHH_PAIR_WORDS(nbx, nby);
+  P.lds_bytes = RHH_PAIR_LDS(nbx, nby);
+  P.per_pair = P.S * P.words * 4;
+  P.over_cap = P.per_pair > cap;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, npairs));
+  return P;
+}
+// given bounds (range != NULL and not both NaN) are used as they are, else the automatic ones; lo == hi: numpy's rule
+inline bool histogram_auto(const double *range) { return !range || (std::isnan(range[0]) && std::isnan(range[1])); }
+inline bool histogram_range_ok(const double *range) {
+  return histogram_auto(range) || (std::isfinite(range[0]) && std::isfinite(range[1]) && range[0] <= range[1] && std::isfinite(range[1] - range[0]));
+}
+// e [nbins + 1] from the bounds, in double: non-decreasing by construction; NaN bounds (a column without a finite value): NaN edges
+// (a constant of magnitude 2^53 or more: lo - 0.5 == lo, the width stays 0, all edges are equal and every row counts in the last,
+// closed bin -- what the counts' definition against the edges gives; the density of a bin without width is NaN)
+inline void histogram_edges(double lo, double hi, int nbins, double *e) {
+  if (lo == hi) { lo -= 0.5; hi += 0.5; }
+  if (std::isnan(lo) || std::isnan(hi)) { for (int i = 0; i <= nbins; i++) e[i] = std::nan(""); return; }
+  const double w = hi - lo;
+  e[0] = lo;
+  for (int i = 1; i < nbins; i++) e[i] = std::min(hi, std::max(e[i - 1], lo + ((double)i * w) / (double)nbins));
+  e[nbins] = hi;
 }
 // ---- predict (device/rh_predict.hip.h) ----
 // that header cannot be included without a generated program around it, so these four are mirrors: RP_WAVE, RP_MAX_TILE, RP_LDS_DOUBLES, RP_TILE_FOR

@@ -466,6 +466,142 @@ def covariance_device(ptr: int, chains: int, iterations: int, nvars: int, device
     return _covariance_result(call, nvars, cols, corr)
 
 
+class Histogram(NamedTuple):
+    """The shape of single parameters (the reference's density(seq, bounds), rainier-notebook package.scala:63-77): for column k
+    (parameter cols[k]) edges [K][nbins + 1], counts [K][nbins] (int64; bin b holds edges[b] <= x < edges[b + 1], the last bin is
+    closed), and the rows that are in no bin: under [K] (x < edges[0], -inf too), over [K] (x > edges[nbins], +inf too), nan [K]."""
+    cols: Tuple[int, ...]
+    edges: np.ndarray
+    counts: np.ndarray
+    under: np.ndarray
+    over: np.ndarray
+    nan: np.ndarray
+
+    @property
+    def density(self) -> np.ndarray:
+        """counts / (counts.sum(axis=1) * widths): np.histogram(..., density=True); a zero-width bin gives NaN"""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            dens = self.counts / (self.counts.sum(axis=1, keepdims=True) * np.diff(self.edges, axis=1))
+        return np.where(np.diff(self.edges, axis=1) == 0.0, np.nan, dens)
+
+
+class Histogram2d(NamedTuple):
+    """The joint shape of pairs of parameters (the reference's scatter / contour, rainier-notebook package.scala:79-98): for pair p
+    = (a, b) xedges [P][nbx + 1], yedges [P][nby + 1], grid [P][nbx][nby] (int64; the rows whose a falls in bin bx and whose b falls
+    in bin by) and outside [P] (the rows with a coordinate out of range or NaN)."""
+    pairs: Tuple[Tuple[int, int], ...]
+    xedges: np.ndarray
+    yedges: np.ndarray
+    grid: np.ndarray
+    outside: np.ndarray
+
+    @property
+    def density(self) -> np.ndarray:
+        """grid / (grid.sum() * bin areas) per pair: np.histogram2d(..., density=True); a zero-area bin gives NaN"""
+        area = np.diff(self.xedges, axis=1)[:, :, None] * np.diff(self.yedges, axis=1)[:, None, :]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            dens = self.grid / (self.grid.sum(axis=(1, 2), keepdims=True) * area)
+        return np.where(area == 0.0, np.nan, dens)
+
+
+def _depth(r):
+    """nesting depth of bounds as written: a number or None 0, (lo, hi) 1, ((xlo, xhi), (ylo, yhi)) 2, a list of those one more
+    (a None stands for any entry, so the deepest entry decides)"""
+    if isinstance(r, np.ndarray):
+        return r.ndim
+    if not isinstance(r, (list, tuple)):
+        return 0
+    return 1 + max((_depth(ri) for ri in r), default=0)
+
+
+def _bounds(r, unit):
+    """one entry's bounds -> a float64 array of shape `unit` ((2,) or (2, 2)); None, at any level: automatic (NaN)"""
+    if r is None:
+        return np.full(unit, np.nan)
+    if len(r) != unit[0]:
+        raise ValueError("bounds are (lo, hi)%s" % (" per axis" if len(unit) == 2 else ""))
+    if len(unit) == 1:
+        return np.array([np.nan if v is None else float(v) for v in r])
+    return np.stack([_bounds(ri, unit[1:]) for ri in r])
+
+
+def _range_arg(rng, shape, what):
+    """None, one set of bounds for every entry, or one per entry (None: automatic) -> a float64 array of `shape` or None.  Which
+    of the two it is is read from the nesting depth, never from the lengths: bounds as deep as one entry's ((lo, hi); for pairs
+    ((xlo, xhi), (ylo, yhi))) hold for all entries, one level more is a list with one set per entry.  So with two columns
+    [(0, 1), (2, 3)] is one set per column and (0, 1) is one set for both; a list of nothing but None is written None."""
+    if rng is None:
+        return None
+    unit = shape[1:]
+    if isinstance(rng, np.ndarray) and rng.dtype != object:      # an array holds no None: its shape says it all
+        if rng.shape != unit and rng.shape != shape:
+            raise ValueError("%s: a range array has the shape of one entry's bounds %s or of all entries' %s" % (what, unit, shape))
+        return np.ascontiguousarray(np.broadcast_to(rng, shape), dtype=np.float64)
+    depth = _depth(rng)
+    if depth == len(unit):
+        a = np.broadcast_to(_bounds(rng, unit), shape)
+    elif depth == len(unit) + 1:
+        if len(rng) != shape[0]:
+            raise ValueError("%s: range holds %d sets of bounds for %d entries" % (what, len(rng), shape[0]))
+        a = np.stack([_bounds(r, unit) for r in rng])
+    else:
+        raise ValueError("%s: range must be bounds for all entries or a list with one set per entry" % what)
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _histogram_result(call, nvars, cols, bins, rng, model=None):
+    """shared by Sampler.histogram and histogram_device: call(cols, ncols, nbins, range, edges, counts, under, over, nan) -> rc"""
+    sel = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+    k, nb = int(nvars) if sel is None else len(sel), int(bins)
+    r = _range_arg(rng, (k, 2), "histogram")
+    edges, counts = np.zeros((k, max(nb, 0) + 1)), np.zeros((k, max(nb, 0)), dtype=np.int64)
+    under, over, nan = (np.zeros(k, dtype=np.int64) for _ in range(3))
+    buf = sel if sel is None or k else np.zeros(1, dtype=np.int32)       # an empty list is a list (refused), not "all columns"
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    _capi.check(call(buf.ctypes.data_as(C.POINTER(C.c_int32)) if sel is not None else None, k if sel is not None else 0, nb,
+                     _capi.dptr(r) if r is not None else None, _capi.dptr(edges), lp(counts), lp(under), lp(over), lp(nan)), model)
+    return Histogram(tuple(range(k)) if sel is None else tuple(sel.tolist()), edges, counts, under, over, nan)
+
+
+def _histogram2d_result(call, pairs, bins, rng, model=None):
+    """shared by Sampler.histogram2d and histogram2d_device: call(pairs, npairs, nbx, nby, range, xedges, yedges, grid, outside) -> rc"""
+    pr = np.ascontiguousarray([[int(a), int(b)] for a, b in pairs], dtype=np.int32).reshape(-1, 2)
+    p = len(pr)
+    nbx, nby = (int(bins), int(bins)) if np.ndim(bins) == 0 else (int(bins[0]), int(bins[1]))
+    r = _range_arg(rng, (p, 2, 2), "histogram2d")
+    xe, ye = np.zeros((p, max(nbx, 0) + 1)), np.zeros((p, max(nby, 0) + 1))
+    grid, outside = np.zeros((p, max(nbx, 0), max(nby, 0)), dtype=np.int64), np.zeros(p, dtype=np.int64)
+    buf = pr if p else np.zeros((1, 2), dtype=np.int32)
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    _capi.check(call(buf.ctypes.data_as(C.POINTER(C.c_int32)), p, nbx, nby, _capi.dptr(r) if r is not None else None, _capi.dptr(xe),
+                     _capi.dptr(ye), lp(grid), lp(outside)), model)
+    return Histogram2d(tuple((int(a), int(b)) for a, b in pr), xe, ye, grid, outside)
+
+
+def histogram_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
+                     thin: int = 1, cols: Optional[Sequence[int]] = None, bins: int = 20, range=None) -> Histogram:
+    """Histograms of the pooled kept iterations first + j * thin of a device buffer [chains][iterations][nvars] (a sampler's draws, a
+    predictor's to_host = False result, Comm.allgather_draws(to_host=False)), binned where the draws are (rh_histogram_device).
+    cols: the parameters asked for, in the result's order (None: all).  range: None (every column between its smallest and largest
+    finite value, found on the device), one (lo, hi) for all columns, or one per column (None or (nan, nan): automatic).  The
+    default of 20 bins is this package's: the reference's comes from a plotting library that is not in its tree."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_histogram_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count,
+                                                      int(thin), *a)
+    return _histogram_result(call, nvars, cols, bins, range)
+
+
+def histogram2d_device(ptr: int, chains: int, iterations: int, nvars: int, pairs: Sequence[Tuple[int, int]], device: int = 0, first: int = 0,
+                       count: Optional[int] = None, thin: int = 1, bins=(32, 32), range=None) -> Histogram2d:
+    """Joint count grids of pairs of parameters over the pooled kept iterations of a device buffer [chains][iterations][nvars]
+    (rh_histogram2d_device).  bins: (nbx, nby) or one number, nbx * nby <= 4096.  range: None (automatic per axis), one
+    ((xlo, xhi), (ylo, yhi)) for all pairs, or one per pair."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_histogram2d_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count,
+                                                        int(thin), *a)
+    return _histogram2d_result(call, pairs, bins, range)
+
+
 def format_precis(names: Sequence[str], summary: Summary) -> str:
     """precis' table (rainier-notebook package.scala:393-417, without the correlations) as a string: Mean, StdDev and the first two
     order statistics of `summary`, %10.2f, one line per parameter."""
@@ -575,6 +711,26 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_covariance(self._h, int(first), count, int(thin), *a)
         return _covariance_result(call, self.model.nVars, cols, corr, self.model._h)
+
+    def histogram(self, first: int = 0, count: Optional[int] = None, thin: int = 1, cols: Optional[Sequence[int]] = None, bins: int = 20,
+                  range=None) -> Histogram:
+        """Histograms of the parameters over the kept iterations first + j * thin of all chains pooled, binned where the draws are
+        (rh_sampler_histogram): the reference's density(seq, bounds).  cols: the parameters asked for, in the result's order (None:
+        all); range: None (every column between its smallest and largest finite value), one (lo, hi) for all columns, or one per
+        column (None or (nan, nan): automatic); count = None: everything completed so far.  The default of 20 bins is this
+        package's: the reference's comes from a plotting library that is not in its tree.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_histogram(self._h, int(first), count, int(thin), *a)
+        return _histogram_result(call, self.model.nVars, cols, bins, range, self.model._h)
+
+    def histogram2d(self, pairs: Sequence[Tuple[int, int]], first: int = 0, count: Optional[int] = None, thin: int = 1, bins=(32, 32),
+                    range=None) -> Histogram2d:
+        """Joint count grids of pairs of parameters over the same window (rh_sampler_histogram2d): what the reference's scatter /
+        contour show.  bins: (nbx, nby) or one number, nbx * nby <= 4096; range: None (automatic per axis), one
+        ((xlo, xhi), (ylo, yhi)) for all pairs, or one per pair.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_histogram2d(self._h, int(first), count, int(thin), *a)
+        return _histogram2d_result(call, pairs, bins, range, self.model._h)
 
     def mass_dense(self) -> np.ndarray:
         """DenseMassMatrix.elements of every chain: [chains][nVars][nVars] (DenseMassMatrixTuner only)."""
