@@ -19,6 +19,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -44,6 +45,9 @@ const char *const kPreludeSrc =
     ;
 static const char *kEngineSrc =
 #include "gen/rh_engine.inc"
+    ;
+static const char *kLaneSrc =
+#include "gen/rh_lane.inc"
     ;
 namespace {
 thread_local std::string g_err;
@@ -146,6 +150,13 @@ struct rh_model {
   hipFunction_t k_grad_fused = nullptr;  // rh_grad_kernel + the mid-trajectory leapfrog update as its prologue (static HMC); absent when the model does not qualify
   hipFunction_t k_absorb = nullptr;      // the fused launches' per-chain records -> state image, before the tick that ends a trajectory
   hipFunction_t k_compact = nullptr;     // active flags -> ascending list of the chains that wait for a gradient (rh_compact_kernel)
+  // the lane walk (rh_grad_lane_kernel: chains in the lanes, rows in scalar registers): a code object of its own, empty / nullptr when
+  // the model does not qualify (lane_eligible) or the kernel is not fit to run
+  std::vector<char> lane_code;
+  hipModule_t lane_module = nullptr;
+  hipFunction_t k_grad_lane = nullptr;
+  int grad_chains_req = 0;               // rh_compile_opts.grad_chains as the caller gave it (0 = automatic)
+  bool lane_tried = false;               // build_lane_code has run (lane_code is final)
   int ncols_max = 0, glm_ncols = 0;
   hipFunction_t k_grad_glm = nullptr;
   bool glm_small = false;  // <= 8 predictors: the plain VALU kernel (the fp64 matrix pipe pays from ~9 predictors on, profiles/r1_c)
@@ -238,6 +249,7 @@ struct rh_sampler {
   void *d_qbuf = nullptr, *d_active = nullptr;
   void *d_rec[2] = {nullptr, nullptr};  // fused launches: the two record buffers (alternating)
   bool fuse = false;  // static HMC on the plain gradient kernel: mid-trajectory updates run as the gradient launch's epilogue
+  bool lane_walk = false;          // the gradient launches are rh_grad_lane_kernel's (lanes_plan.hpp walk_is_lane; fixed at creation)
   std::vector<Lane> lanes;         // one, or two halves of the chains on two streams (lanes_plan.hpp)
   std::vector<rh_chain_stats_dev> last_stats;
   int64_t grads_at_reset = 0;
@@ -587,8 +599,72 @@ void build_code(rh_model *m) {
   }
 }
 
+// The lane walk's code object: the model's own translation unit once more with rh_lane.hip.h behind it (rh_grad_lane_kernel).  Kept
+// apart from the models' *.hsaco (like the predictors'): only that kernel is taken from it.  Built for the models the walk fits
+// -- plain row streaming, chain-group size left to the engine, R rows of every column in scalar registers, the workgroup's sums in
+// LDS -- and kept only if the kernel passes the engine's own fitness checks without a spill or a byte of scratch.
+int lane_ncols_max(const rh_model *m) {
+  int ncols_max = 0;
+  for (const auto &T : m->prog.targets) ncols_max = std::max<int>(ncols_max, (int)T.n_cols);
+  return ncols_max;
+}
+bool lane_eligible(const rh_model *m) {
+  const int ncols_max = lane_ncols_max(m);
+  const bool glm = m->has_glm && m->n_row_targets_hint == 1 && !m->glm_small;
+  return m->n_row_targets_hint > 0 && !m->info.gather_mode && !m->info.bign && m->eopt.chunk == 0 && !glm && !m->lk_lds &&
+         m->grad_chains_req == 0 && !m->want_nuts && rh_plan::lane_walk_fits_r(ncols_max, m->nacc_max, 4);
+}
+// Rows per scalar request: 8 where the kernel fits, else 4 (a strict build's row code leaves fewer scalar registers); a shape that
+// does not compile or does not fit leaves a marker in the cache, like an abandoned attempt of build_code, and is not compiled again.
+void build_lane_code(rh_model *m) {
+  m->lane_code.clear();
+  m->lane_tried = true;
+  if (!lane_eligible(m)) return;
+  const char *e = rh::knob("RH_HIPRTC_EXTRA");
+  const std::string extra = e ? e : "";
+  const bool cache = !std::getenv("RH_NO_KERNEL_CACHE");
+  for (int R : {8, 4}) {
+    if (!rh_plan::lane_walk_fits_r(lane_ncols_max(m), m->nacc_max, R)) continue;
+    const std::string src = (R == rh_plan::kLaneR ? std::string() : "#define RH_LANE_R " + std::to_string(R) + "\n") + m->source + "\n" + kLaneSrc;
+    const std::string marker = cache_path(m->arch, src, extra) + ".lane.unfit";
+    std::vector<char> mk;
+    if (cache && read_file(marker, mk) && std::string(mk.begin(), mk.end()).compare(0, marker_header().size(), marker_header()) == 0) continue;
+    bool fit = false;
+    std::string why;
+    rh::KernelMeta km;
+    std::vector<char> code;
+    try {
+      code = build_source(m->arch, src, extra, ".lane.co");
+      fit = kernel_health(code, "rh_grad_lane_kernel", &why) == KH_OK && rh::kernel_meta(code, "rh_grad_lane_kernel", km) && km.vgpr_spills == 0 &&
+            km.sgpr_spills == 0 && km.scratch_bytes == 0 && rh::kernel_touches_scratch(code, "rh_grad_lane_kernel") == 0;
+    } catch (const Fail &f) { why = f.msg; }   // (row code the walk cannot hold does not compile)
+    if (rh::knob("RH_BUILD_LOG"))
+      std::fprintf(stderr, "[rh build] lane walk R %d: vgprs %ld sgprs %ld spills %ld/%ld scratch %ld: %s %s\n", R, km.vgprs, km.sgprs, km.vgpr_spills,
+                   km.sgpr_spills, km.scratch_bytes, fit ? "fit" : "unfit", why.c_str());
+    if (fit) { m->lane_code = code; return; }
+    if (cache) {
+      std::remove((cache_path(m->arch, src, extra) + ".lane.co").c_str());
+      const std::string text = marker_header() + "\nrh_grad_lane_kernel\n";   // (the form of build_code's markers: the unfit kernels)
+      write_file(marker, std::vector<char>(text.begin(), text.end()));
+    }
+  }
+}
+// The lane walk's kernel, built and loaded the first time a sampler or an evaluation could take it (nullptr: the model has none)
+hipFunction_t fit_kernel(const std::vector<char> &code, hipModule_t module, const char *name, std::string *why = nullptr);
+hipFunction_t ensure_lane(rh_model *m) {
+  std::lock_guard<std::recursive_mutex> lk(m->engine_mu);
+  if (m->k_grad_lane) return m->k_grad_lane;
+  if (!m->k_grad || !m->k_tick || m->info.gather_mode) return nullptr;
+  if (!m->lane_tried) build_lane_code(m);
+  if (m->lane_code.empty() || m->lane_module) return nullptr;
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipModuleLoadData(&m->lane_module, m->lane_code.data()));
+  m->k_grad_lane = fit_kernel(m->lane_code, m->lane_module, "rh_grad_lane_kernel", nullptr);
+  return m->k_grad_lane;
+}
+
 // kernel `name` of `module` if it is fit to run (kernel_health); otherwise nullptr and the reason
-hipFunction_t fit_kernel(const std::vector<char> &code, hipModule_t module, const char *name, std::string *why = nullptr) {
+hipFunction_t fit_kernel(const std::vector<char> &code, hipModule_t module, const char *name, std::string *why) {
   std::string w;
   const int h = kernel_health(code, name, &w);
   if (h != KH_OK) {
@@ -766,6 +842,7 @@ int apply_compile_opts(rh_model *m, const rh_compile_opts *opts) {
   if (opts->grad_chains < 0 || opts->grad_chains > 16 || opts->grad_unroll < 0 || opts->grad_unroll > 16)
     throw Fail{RH_E_INVALID, "grad_chains / grad_unroll out of range [0,16]"};
   m->eopt.grad_chains = opts->grad_chains; m->eopt.grad_unroll = opts->grad_unroll;
+  m->grad_chains_req = opts->grad_chains;
   m->eopt.factor_outputs = opts->factor_outputs != 0;
   if (opts->with_nuts < 0 || opts->with_nuts > 7) throw Fail{RH_E_INVALID, "with_nuts: unknown variant bits"};
   m->want_nuts = opts->with_nuts != 0;
@@ -1160,7 +1237,9 @@ extern "C" int rh_model_clone(const rh_model *src, int32_t device, rh_model **ou
     m->shape_guessed = src->shape_guessed; m->synth_cols = src->synth_cols; m->ncols_max = src->ncols_max; m->glm_ncols = src->glm_ncols;
     m->device = dev;
     m->arch = device_arch(dev);
-    if (m->arch == src->arch) m->code = src->code; else build_code(m);   // (a mixed node: compiled or fetched from the cache for that architecture)
+    m->grad_chains_req = src->grad_chains_req;
+    if (m->arch == src->arch) { m->code = src->code; m->lane_code = src->lane_code; m->lane_tried = src->lane_tried; }
+    else build_code(m);   // (a mixed node: compiled or fetched from the cache for that architecture)
     load_module(m);
     if (m->want_nuts) (void)load_variant(m, 1);
     // observation columns and group offsets: device to device (src's copies are immutable after rh_model_create)
@@ -1203,6 +1282,7 @@ extern "C" void rh_model_destroy(rh_model *m) {
     if (m->stream) hipStreamDestroy(m->stream);
     for (int v = 1; v < 8; v++)  // [0] aliases the base module
       if (m->variants[v].module && m->variants[v].module != m->module) hipModuleUnload(m->variants[v].module);
+    if (m->lane_module) hipModuleUnload(m->lane_module);
     if (m->module) hipModuleUnload(m->module);
   }
   delete m;
@@ -1310,6 +1390,7 @@ extern "C" int rh_lower_report_data(const void *rir, size_t rir_len, const doubl
     m.arch = arch && *arch ? arch : "gfx950";
     if (code_size) {          // (nullptr: source only -- the CPU suite's host emulation of the generated code)
       build_code(&m);         // may lower again with a smaller row-loop unroll: the source returned is the one that was compiled
+      build_lane_code(&m);
       *code_size = m.code.size();
     }
     if (src_out) {
@@ -1334,6 +1415,10 @@ extern "C" int rh_lower_report_data(const void *rir, size_t rir_len, const doubl
                       " chunk=" + std::to_string(m.eopt.chunk) + " bigu=" + std::to_string(m.eopt.big_unroll) + " gather=" + std::to_string((int)m.info.gather_mode) + " row_targets=" + std::to_string(m.n_row_targets_hint) + "\n";
       r += code_report(m.code, "base");
       if (!vcode.empty()) r += code_report(vcode, "variant" + std::to_string(opts->with_nuts & 7));
+      if (!m.lane_code.empty()) {   // (of the lane walk's code object only the kernel the engine takes from it)
+        std::istringstream all(code_report(m.lane_code, "lane"));
+        for (std::string ln; std::getline(all, ln);) if (ln.find("rh_grad_lane_kernel") != std::string::npos) r += ln + "\n";
+      }
       *report = (char *)std::malloc(r.size() + 1); std::memcpy(*report, r.c_str(), r.size() + 1);
     }
   });
@@ -1479,14 +1564,39 @@ int default_nsplit(const rh_model *m, int chains) {
   return (int)std::min<int64_t>(nsplit, cap);
 }
 
+// the lane walk: RH_GRAD_WALK=tile|lane (RH_DIAG) forces the walk; total_chains = the chains of the whole sampler, all shards
+int64_t lane_max_rows(const rh_model *m) {
+  int64_t max_rows = 1;
+  for (size_t t = 0; t < m->prog.targets.size(); t++) if (m->prog.targets[t].n_cols) max_rows = std::max<int64_t>(max_rows, m->data.nrows[t]);
+  return max_rows;
+}
+thread_local int g_total_chains = 0;   // set by rh_sample_multi's shard threads around rh_sample
+thread_local int g_shard_walk = -1;    // ... with the walk rh_sample_multi chose for all of its shards (0 tile, 1 lane; -1: no shards)
+bool walk_is_lane(rh_model *m, bool static_hmc, int total_chains) {
+  if (g_shard_walk >= 0) return g_shard_walk == 1 && ensure_lane(m) != nullptr;
+  int forced = 0;
+  if (const char *e = rh::knob("RH_GRAD_WALK")) forced = std::strcmp(e, "tile") == 0 ? 1 : (std::strcmp(e, "lane") == 0 ? 2 : 0);
+  if (!rh_plan::walk_is_lane(true, static_hmc, m->grad_chains_req, total_chains, lane_max_rows(m), forced)) return false;   // (no reason to build the kernel)
+  return ensure_lane(m) != nullptr;
+}
+int lane_nsplit(const rh_model *m, int total_chains) {
+  return rh_plan::lane_nsplit(total_chains, lane_max_rows(m));
+}
+
 // one batched gradient launch of the tick engine: whichever row-streaming kernel the model was lowered to
 // (rh_grad_gather_kernel [+ rh_grad_gather_scan_kernel] | rh_grad_glm_kernel | rh_grad_kernel), per-split partial sums -> d_partial.
 // The grid covers every chain; with a list (d_list / d_nlive; nullptr = all `chains`) slot s of the launch is chain list[s] and the
 // workgroups of the slots past the live count -- the last of the grid -- return at once.
 // d_vflag: the chains' request flags (rh_tick_kernel: 2 = gradient only, the log-density of that evaluation is never read) or nullptr.
 void launch_grad(rh_model *m, GatherBufs *gb, void *d_q, void *d_list, void *d_nlive, void *d_vflag, void *d_partial, void *d_graderr, void *d_running,
-                 int chains, int nsplit, int xcd, hipStream_t stream = nullptr) {
+                 int chains, int nsplit, int xcd, hipStream_t stream = nullptr, bool lane_walk = false) {
   if (!stream) stream = m->stream;
+  if (lane_walk) {   // rh_grad_lane_kernel: 64 C chains per group, W wavefronts per workgroup, rh_grad_kernel's arguments
+    void *la[] = {&m->data, &d_q, &d_list, &d_nlive, &d_vflag, &d_partial, &d_graderr, &d_running, &chains, &nsplit, &xcd};
+    const int lgroups = (chains + rh_plan::kLaneGroup - 1) / rh_plan::kLaneGroup;
+    launch(m->k_grad_lane, (unsigned)(lgroups * nsplit), 64 * rh_plan::kLaneW, stream, la);
+    return;
+  }
   const int ngroups = (chains + m->grad_k - 1) / m->grad_k;
   if (m->info.gather_mode) {
     void *ga[] = {&m->data, &gb->gd, &d_q, &d_list, &d_nlive, &d_vflag, &d_partial, &d_graderr, &d_running, &chains, &nsplit};
@@ -1539,7 +1649,8 @@ extern "C" int rh_density_eval_ex(rh_model *m, const double *q, int32_t chains, 
       // the tick engine's gradient path exactly as the sampler drives it: the row-streaming gradient kernel fills the
       // per-split partial sums (and, in gather mode, the scatter sums) for all chains, the finish kernel combines them in
       // the same fixed order as rh_tick_kernel (rh_combine_chain) -- so parity tests reach the kernels the bench times
-      int nsplit = grad_splits > 0 ? grad_splits : (m->info.gather_mode ? 64 : default_nsplit(m, chains));
+      const bool lane_walk = walk_is_lane(m, false, chains);   // (only where RH_GRAD_WALK=lane asks for it)
+      int nsplit = grad_splits > 0 ? grad_splits : (m->info.gather_mode ? 64 : lane_walk ? lane_nsplit(m, chains) : default_nsplit(m, chains));
       GatherBufs gb;
       if (m->info.gather_mode) gb.build(m, chains, nsplit);
       const size_t pbytes = sizeof(double) * (size_t)m->n_row_targets * nsplit * chains * m->nacc_max;
@@ -1569,7 +1680,7 @@ extern "C" int rh_density_eval_ex(rh_model *m, const double *q, int32_t chains, 
           dnl = bnl->p;
         }
       }
-      launch_grad(m, &gb, dq, blist.p, dnl, nullptr, bpart.p, de, brun.p, chains, nsplit, xcd);
+      launch_grad(m, &gb, dq, blist.p, dnl, nullptr, bpart.p, de, brun.p, chains, nsplit, xcd, nullptr, lane_walk);
       void *dpart = bpart.p;
       if (m->info.gather_mode) {
         void *fa[] = {&m->data, &gb.gd, &dq, &dpart, &dl, &dg, &de, &ch, &nsplit, &dtot};
@@ -1786,8 +1897,13 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
     HIPCHK(hipEventCreate(&s->e1));
     s->last_stats.resize(chains);
     if (s->tick_engine) {
+      // The walk of the gradient launches, for the sampler's whole life (warm-up, every request of a trajectory): the lane walk where
+      // lanes_plan.hpp's rule says so, from the model, the configuration and the chains of the WHOLE sampler.  It has no fused form
+      // (each workgroup would combine 64 C chains x nsplit partial sums in its prologue, nsplit^2 x chains sums per launch: more
+      // bytes than the rows), so its trajectories run launch, tick, launch.
+      s->lane_walk = walk_is_lane(m, cfg->sampler == RH_SAMPLER_HMC, g_total_chains > 0 ? g_total_chains : chains);
       int nsplit = cfg->grad_splits;
-      if (nsplit <= 0) nsplit = default_nsplit(m, chains);
+      if (nsplit <= 0) nsplit = s->lane_walk ? lane_nsplit(m, g_total_chains > 0 ? g_total_chains : chains) : default_nsplit(m, chains);
       // The dynamic samplers' trajectories end at different launches (EHMC: DefaultConfig's, sampler/Sampler.scala:17-27; NUTS:
       // BASELINE's): their launches serve the LISTED chains only (rh_compact_kernel), and the rows are cut into 8 x as many, shorter
       // splits as a lock-step launch needs, so that a launch with few live chains still spreads over the machine (as long as a
@@ -1813,7 +1929,7 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
       {  // The fused launch (rh_grad_fused_kernel: static HMC's mid-trajectory update as the gradient launch's prologue) needs the
          // base sampler-kernel variant (its state layout is compiled into the gradient module), the plain VALU gradient kernel and
          // a lock-step sampler.  Chains are bit-identical with and without it (tests/test_gpu_fused.py); RH_FUSE=0 turns it off.
-        bool fuse = m->k_grad_fused && m->k_absorb && s->k_tick == m->k_tick && cfg->sampler == RH_SAMPLER_HMC && !m->k_grad_glm;
+        bool fuse = m->k_grad_fused && m->k_absorb && s->k_tick == m->k_tick && cfg->sampler == RH_SAMPLER_HMC && !m->k_grad_glm && !s->lane_walk;
         if (const char *e = rh::knob("RH_FUSE")) fuse = fuse && std::atoi(e) != 0;
         if (fuse) {
           const size_t rec_bytes = sizeof(uint64_t) * rec_u64 * chains;
@@ -1827,8 +1943,8 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
       // count (2: wherever there are two chain groups to part).
       int forced = 0;
       if (const char *e = rh::knob("RH_LANES")) forced = std::atoi(e) == 1 ? 1 : (std::atoi(e) == 2 ? 2 : 0);
-      const rh_plan::LaneCut cut = rh_plan::lanes_cut(chains, m->k_grad_glm ? 16 : m->grad_k, nsplit, m->k_grad_glm ? m->glm_w : 1,
-                                                      device_cus(m->device), forced);
+      const rh_plan::LaneCut cut = rh_plan::lanes_cut(chains, s->lane_walk ? rh_plan::kLaneGroup : m->k_grad_glm ? 16 : m->grad_k, nsplit,
+                                                      s->lane_walk ? rh_plan::kLaneW : m->k_grad_glm ? m->glm_w : 1, device_cus(m->device), forced);
       s->lanes.resize((size_t)cut.lanes);
       const size_t iters_alloc = (size_t)cfg->iterations;   // (a chain's draws are addressed as chain * cfg.iterations * n)
       for (int li = 0; li < cut.lanes; li++) {
@@ -1931,7 +2047,7 @@ void advance_to_ticks(rh_sampler *s, int it_stop) {
   };
   auto grad = [&](Lane &L, void *partial) {
     launch_grad(m, L.gb, L.qbuf, L.d_list, s->compact ? L.d_nlive : nullptr /* (without compaction d_list stays the identity) */,
-                value_free ? L.active : nullptr, partial, L.d_graderr, L.d_running, L.chains, nsplit, xcd, L.stream);
+                value_free ? L.active : nullptr, partial, L.d_graderr, L.d_running, L.chains, nsplit, xcd, L.stream, s->lane_walk);
   };
   // gradient at the point the PREVIOUS launch's gradient moves every chain to (rh_fused_prologue); no tick between the two
   auto grad_fused = [&](Lane &L, void *partial_in, void *partial_out, void *rec_in, void *rec_out) {
@@ -2258,7 +2374,7 @@ extern "C" int rh_sampler_timing(rh_sampler *s, rh_timing *out, int reset) {
     out->kernel_ms = s->kernel_ms; out->total_ms = s->total_ms; out->launches = s->launches;
     out->density_evals = grads - s->grads_at_reset;
     out->row_chain_evals = out->density_evals * s->m->rows_total;
-    std::snprintf(out->dominant_kernel, sizeof out->dominant_kernel, s->tick_engine ? (s->m->info.gather_mode ? "rh_grad_gather_kernel" : s->m->k_grad_glm ? "rh_grad_glm_kernel" : (s->fuse && s->warmed && s->cfg.hmc_steps > 1) ? "rh_grad_fused_kernel" : "rh_grad_kernel") : "rh_chain_kernel");
+    std::snprintf(out->dominant_kernel, sizeof out->dominant_kernel, s->tick_engine ? (s->m->info.gather_mode ? "rh_grad_gather_kernel" : s->m->k_grad_glm ? "rh_grad_glm_kernel" : s->lane_walk ? "rh_grad_lane_kernel" : (s->fuse && s->warmed && s->cfg.hmc_steps > 1) ? "rh_grad_fused_kernel" : "rh_grad_kernel") : "rh_chain_kernel");
     out->chain_slots = s->tick_engine ? s->chain_slots : out->density_evals;
     out->steady_kernel_ms = s->steady_ms; out->steady_launches = s->steady_launches; out->steady_density_evals = s->steady_evals;
     if (reset) { s->kernel_ms = 0; s->total_ms = 0; s->launches = 0; s->grads_at_reset = grads; s->chain_slots = 0; s->steady_ms = 0; s->steady_launches = 0; s->steady_evals = 0; }
@@ -2295,7 +2411,10 @@ extern "C" int rh_sample_multi(rh_model *const *models, int32_t n_models, const 
   // the tick engine's row-split count is derived from the chain count; fix it from the TOTAL here so that every shard sums its
   // rows in the same order as the unsharded call would (bit-identical draws for every shard count)
   int splits_all = cfg->grad_splits;
-  if (splits_all <= 0 && models[0]->n_row_targets > 0) splits_all = default_nsplit(models[0], chains);
+  // ... and so is the walk: the lane walk only where every shard's model has the kernel (a mixed node may not), decided here once
+  bool lane_all = models[0]->n_row_targets > 0;
+  for (int g = 0; g < G && lane_all; g++) lane_all = walk_is_lane(models[g], cfg->sampler == RH_SAMPLER_HMC, chains);
+  if (splits_all <= 0 && models[0]->n_row_targets > 0) splits_all = lane_all ? lane_nsplit(models[0], chains) : default_nsplit(models[0], chains);
   std::vector<int> first((size_t)G + 1, 0);
   for (int g = 0; g < G; g++) first[(size_t)g + 1] = first[(size_t)g] + chains / G + (g < chains % G ? 1 : 0);
   std::vector<int> rcs((size_t)G, RH_OK);
@@ -2308,8 +2427,10 @@ extern "C" int rh_sample_multi(rh_model *const *models, int32_t n_models, const 
       c.grad_splits = splits_all;
       if (cfg->rng_next_gaussian) c.rng_next_gaussian = cfg->rng_next_gaussian + c0;
       const size_t per_chain = (size_t)cfg->iterations * (size_t)nv;
+      g_total_chains = chains; g_shard_walk = lane_all ? 1 : 0;   // (this shard thread's: walk and splits are the whole sampler's)
       rcs[(size_t)g] = rh_sample(models[g], &c, seeds + c0, nc, draws ? draws + (size_t)c0 * per_chain : nullptr,
                                  mass_diag ? mass_diag + (size_t)c0 * nv : nullptr, stats ? stats + c0 : nullptr);
+      g_total_chains = 0; g_shard_walk = -1;
       if (rcs[(size_t)g] != RH_OK) errs[(size_t)g] = rh_last_error(models[g]);
     });
   for (auto &t : th) t.join();

@@ -28,6 +28,43 @@ inline LaneCut lanes_cut(int chains, int group, int nsplit, int waves_per_wg, in
   return {2, {0, cut}, {cut, chains - cut}};
 }
 
+// ---- the lane walk (rh_grad_lane_kernel) ----
+// Its shape: W wavefronts per workgroup, R rows per scalar request, C chains per lane (RH_LANE_W / _R / _C of rh_lane.hip.h), a
+// chain group of 64 C chains; measured on cfg 2, profiles/lane_walk_cfg2.
+constexpr int kLaneW = 8, kLaneR = 8, kLaneC = 2, kLaneGroup = 64 * kLaneC;
+// Where the lane walk is chosen (profiles/lane_walk_cfg2/threshold_sweep.jsonl: tile against lane walk, same machine, static HMC
+// L = 32): at 1e6 rows it wins by 14-18 % from 512 to 2048 chains and by 5 % at 256; at 70 000 rows it LOSES 17-20 % at 1024 and
+// 2048 chains, where a launch takes 20-30 us and the tick behind every launch (the walk has no fused form) costs more than the
+// kernel gains.  So: at least 512 chains and 5.12e8 row-chain evaluations per gradient, the smallest point measured with a clear gain.
+constexpr int kLaneMinChains = 512;
+constexpr long long kLaneMinEvals = 512LL * 1000000LL;
+// does a model's row code fit the walk at R rows per request: R rows of every column in scalar registers (2 each, 64 of the ~100
+// there are), and the W wavefronts' sums of a chain group in 64 KB of LDS
+inline bool lane_walk_fits_r(int ncols_max, int nacc_max, int r) {
+  return ncols_max >= 1 && ncols_max * r * 2 <= 64 && nacc_max >= 1 && (long long)kLaneW * kLaneC * nacc_max * 64 * 8 <= 64 * 1024;
+}
+inline bool lane_walk_fits(int ncols_max, int nacc_max) { return lane_walk_fits_r(ncols_max, nacc_max, kLaneR); }
+// Which walk a sampler's gradient launches take -- decided once, at its creation, from the model, the sampler's configuration and
+// the TOTAL chain count only (like nsplit; rh_sample_multi hands its decision to its shards).  model_has_lane: the lane kernel was
+// built and is fit to run; grad_chains: the caller's rh_compile_opts.grad_chains (an explicit K asks for K chains per wavefront,
+// which is the tile kernel); max_rows: the rows of the model's longest row target; forced: 0 = this rule, 1 = tile, 2 = lane
+// wherever the model has it (RH_GRAD_WALK).
+inline bool walk_is_lane(bool model_has_lane, bool static_hmc, int grad_chains, int total_chains, long long max_rows, int forced) {
+  if (!model_has_lane || forced == 1) return false;
+  if (forced == 2) return true;
+  return static_hmc && grad_chains == 0 && total_chains >= kLaneMinChains && (long long)total_chains * max_rows >= kLaneMinEvals;
+}
+// The lane walk's row splits per chain group: eight wavefronts per SIMD of a 256-CU device (8192) over groups x splits x W, a
+// multiple of 8 for the XCD mapping, and no more than leave a split 512 rows (a block of R rows for each of the W wavefronts,
+// eight times over).  cfg 2: 8 groups -> 128 splits.
+inline int lane_nsplit(int total_chains, long long max_rows) {
+  const long long ngroups = std::max(1, (total_chains + kLaneGroup - 1) / kLaneGroup);
+  long long nsplit = std::max<long long>(1, (8192 + ngroups * kLaneW - 1) / (ngroups * kLaneW));
+  nsplit = ((nsplit + 7) / 8) * 8;
+  const long long cap = std::max<long long>(8, (max_rows / 512) / 8 * 8);
+  return (int)std::min(nsplit, cap);
+}
+
 // ---- the busy share of overlapping spans ----
 // n spans [t0[i], t1[i]] on one time base (t1 < t0 is read as an empty span at t0).  share[i] = the integral over span i of
 // 1 / (spans open at that instant); the shares add up to the length of the union of the spans, which is the value returned.
