@@ -157,6 +157,7 @@ struct rh_model {
   hipFunction_t k_grad_lane = nullptr;
   int grad_chains_req = 0;               // rh_compile_opts.grad_chains as the caller gave it (0 = automatic)
   bool lane_tried = false;               // build_lane_code has run (lane_code is final)
+  int lane_r = 0;                        // rows per scalar request of the kernel in lane_code (8 or 4; 0: none)
   int ncols_max = 0, glm_ncols = 0;
   hipFunction_t k_grad_glm = nullptr;
   bool glm_small = false;  // <= 8 predictors: the plain VALU kernel (the fp64 matrix pipe pays from ~9 predictors on, profiles/r1_c)
@@ -618,6 +619,7 @@ bool lane_eligible(const rh_model *m) {
 // does not compile or does not fit leaves a marker in the cache, like an abandoned attempt of build_code, and is not compiled again.
 void build_lane_code(rh_model *m) {
   m->lane_code.clear();
+  m->lane_r = 0;
   m->lane_tried = true;
   if (!lane_eligible(m)) return;
   const char *e = rh::knob("RH_HIPRTC_EXTRA");
@@ -641,7 +643,7 @@ void build_lane_code(rh_model *m) {
     if (rh::knob("RH_BUILD_LOG"))
       std::fprintf(stderr, "[rh build] lane walk R %d: vgprs %ld sgprs %ld spills %ld/%ld scratch %ld: %s %s\n", R, km.vgprs, km.sgprs, km.vgpr_spills,
                    km.sgpr_spills, km.scratch_bytes, fit ? "fit" : "unfit", why.c_str());
-    if (fit) { m->lane_code = code; return; }
+    if (fit) { m->lane_code = code; m->lane_r = R; return; }
     if (cache) {
       std::remove((cache_path(m->arch, src, extra) + ".lane.co").c_str());
       const std::string text = marker_header() + "\nrh_grad_lane_kernel\n";   // (the form of build_code's markers: the unfit kernels)
@@ -1238,7 +1240,7 @@ extern "C" int rh_model_clone(const rh_model *src, int32_t device, rh_model **ou
     m->device = dev;
     m->arch = device_arch(dev);
     m->grad_chains_req = src->grad_chains_req;
-    if (m->arch == src->arch) { m->code = src->code; m->lane_code = src->lane_code; m->lane_tried = src->lane_tried; }
+    if (m->arch == src->arch) { m->code = src->code; m->lane_code = src->lane_code; m->lane_r = src->lane_r; m->lane_tried = src->lane_tried; }
     else build_code(m);   // (a mixed node: compiled or fetched from the cache for that architecture)
     load_module(m);
     if (m->want_nuts) (void)load_variant(m, 1);
@@ -1415,9 +1417,13 @@ extern "C" int rh_lower_report_data(const void *rir, size_t rir_len, const doubl
                       " chunk=" + std::to_string(m.eopt.chunk) + " bigu=" + std::to_string(m.eopt.big_unroll) + " gather=" + std::to_string((int)m.info.gather_mode) + " row_targets=" + std::to_string(m.n_row_targets_hint) + "\n";
       r += code_report(m.code, "base");
       if (!vcode.empty()) r += code_report(vcode, "variant" + std::to_string(opts->with_nuts & 7));
-      if (!m.lane_code.empty()) {   // (of the lane walk's code object only the kernel the engine takes from it)
+      if (!m.lane_code.empty()) {   // (of the lane walk's code object only the kernel the engine takes from it, which is fit: with
+        // the rows per scalar request it was built for and its static LDS)
+        rh::KernelMeta km;
+        rh::kernel_meta(m.lane_code, "rh_grad_lane_kernel", km);
         std::istringstream all(code_report(m.lane_code, "lane"));
-        for (std::string ln; std::getline(all, ln);) if (ln.find("rh_grad_lane_kernel") != std::string::npos) r += ln + "\n";
+        for (std::string ln; std::getline(all, ln);)
+          if (ln.find("rh_grad_lane_kernel") != std::string::npos) r += ln + " lane_r=" + std::to_string(m.lane_r) + " lds=" + std::to_string(km.lds_bytes) + "\n";
       }
       *report = (char *)std::malloc(r.size() + 1); std::memcpy(*report, r.c_str(), r.size() + 1);
     }

@@ -209,9 +209,11 @@ bool kernel_meta(const std::vector<char> &code, const std::string &name, KernelM
   if (at == std::string::npos) return false;
   size_t next = find(mstr(".name"), at + 1, code.size());
   if (next == std::string::npos) next = code.size();
-  auto num = [&](const char *key, long &v) {
+  // (last: the key's last occurrence in [from, to) instead of its first)
+  auto num_in = [&](const char *key, long &v, size_t from, size_t to, bool last) {
     const std::string k = mstr(key);
-    const size_t p = find(k, at, next);
+    size_t p = find(k, from, to);
+    for (size_t n = p; last && n != std::string::npos; n = find(k, n + 1, to)) p = n;
     if (p == std::string::npos || p + k.size() >= code.size()) return false;
     const unsigned char *q = (const unsigned char *)code.data() + p + k.size();
     const size_t left = code.size() - (p + k.size());
@@ -221,8 +223,11 @@ bool kernel_meta(const std::vector<char> &code, const std::string &name, KernelM
     if (q[0] == 0xce && left >= 5) { v = (long)q[1] << 24 | (long)q[2] << 16 | (long)q[3] << 8 | q[4]; return true; }
     return false;
   };
+  auto num = [&](const char *key, long &v) { return num_in(key, v, at, next, false); };
   out.found = num(".vgpr_spill_count", out.vgpr_spills) && num(".sgpr_spill_count", out.sgpr_spills) && num(".vgpr_count", out.vgprs) &&
               num(".sgpr_count", out.sgprs) && num(".private_segment_fixed_size", out.scratch_bytes);
+  // ".group_segment_fixed_size" sorts ahead of ".name": the kernel's own is the last one in front of its name
+  (void)num_in(".group_segment_fixed_size", out.lds_bytes, 0, at, true);
   return out.found;
 }
 

@@ -183,6 +183,7 @@ bool emit_predict(const Program &p, const EmitOptions &o, std::string &defines, 
 struct KernelMeta {
   bool found = false;
   long vgprs = -1, sgprs = -1, vgpr_spills = -1, sgpr_spills = -1, scratch_bytes = -1;
+  long lds_bytes = -1;   // static LDS (.group_segment_fixed_size); -1 when the note does not give it (not part of `found`)
 };
 // the kernel's entry of the AMDGPU metadata note; false (found = false) when any of the fields is missing
 bool kernel_meta(const std::vector<char> &code, const std::string &name, KernelMeta &out);

@@ -51,8 +51,9 @@ def _check_tiled(spec, model, distinct, chains, seed, tol, label):
 
 
 def test_cfg2_linreg_1e6_rows_1024_chains_bench_build_vs_oracle():
-    """cfg 2 exactly as bench.py builds it: 3 covariates x 1e6 rows, 1024 chains, fp_contract + factor_outputs + K = 8
-    -> rh_grad_kernel + tick combine, all 1024 chains against the oracle."""
+    """cfg 2 at its benched size through the TILE walk: 3 covariates x 1e6 rows, 1024 chains, fp_contract + factor_outputs and an
+    explicit K = 8 -- a request for the tile kernel (bench.py itself leaves K to the engine, which then takes the lane walk: the
+    test of the benched configuration below) -> rh_grad_kernel + tick combine, all 1024 chains against the oracle."""
     spec = models.linreg(n=1_000_000, k=3)
     m = R.Model(spec, device=0, fp_contract=True, factor_outputs=True, grad_chains=8)
     assert "#define RH_GRAD_K 8" in m.hip_source and "#define RH_FP_CONTRACT 1" in m.hip_source
@@ -71,14 +72,15 @@ def test_cfg2_linreg_1e6_rows_1024_chains_bench_build_vs_oracle():
 
 
 def test_cfg2_headline_kernel_at_its_benched_size_fused_vs_two_launches_vs_oracle(monkeypatch):
-    """The judged bench line's dominant kernel is rh_grad_fused_kernel at 1e6 rows x 1024 chains; the oracle check above goes through
+    """With an explicit K = 8 the dominant kernel at 1e6 rows x 1024 chains is rh_grad_fused_kernel (the tile walk's fused form; the
+    judged bench line leaves K to the engine and runs rh_grad_lane_kernel: the test below); the oracle check above goes through
     rh_grad_kernel.  This closes the link at the benched size (VERDICT r5 next #4a): two static-HMC iterations (L = 32, as bench.py
     runs them) through the fused launches are (1) the same chains bit for bit as the two-launch schedule (RH_FUSE=0), all 1024, and
     (2) two of them within 1e-9 of the ORACLE's chains (oracle/sampler.c on the same 1e6 rows; tame dynamics -- a static step, identity
     mass -- so that rounding differences of the row sums do not grow along the trajectory)."""
     from tests.test_gpu_parity import _oracle_cfg
     spec = models.linreg(n=1_000_000, k=3)
-    m = R.Model(spec, device=0, fp_contract=True, factor_outputs=True, grad_chains=8)      # bench.py's build
+    m = R.Model(spec, device=0, fp_contract=True, factor_outputs=True, grad_chains=8)      # bench.py's build but for the explicit K
     cfg = R.make_config(2, 0, R.HMCSampler(32), R.StaticStepSize(2e-4), R.IdentityMassMatrixTuner(), engine=_capi.ENGINE_TICK)
     seeds = [1000 + c for c in range(1024)]                                                 # bench.py's seeds
 
@@ -97,6 +99,52 @@ def test_cfg2_headline_kernel_at_its_benched_size_fused_vs_two_launches_vs_oracl
     monkeypatch.delenv("RH_FUSE")
     assert plain[1] == "rh_grad_kernel"
     assert np.array_equal(fused[0], plain[0]) and fused[2] == plain[2]
+
+
+def test_cfg2_benched_configuration_takes_the_lane_walk_vs_oracle(monkeypatch):
+    """cfg 2 as bench.py builds and runs it -- fp_contract + factor_outputs, the chain-group size left to the engine, static HMC with
+    L = 32 -- with nothing forced: at 1024 chains x 1e6 rows the rule (csrc/lanes_plan.hpp walk_is_lane) picks the lane walk with its
+    own 128 row splits and the automatic cut into two lanes of 512 chains.  Two iterations: rh_grad_lane_kernel is the dominant
+    kernel, every chain took 64 leapfrog steps, two chains are within 1e-9 of the ORACLE's (tame dynamics, as in the fused test
+    above), and all 1024 are the same bits in one lane and in two.  The rule's chain threshold: the lane kernel at 512 chains, the tile
+    walk's fused kernel at 511.  The density through the same walk (rh_density_eval_ex applies the rule only where RH_GRAD_WALK
+    asks) at 1024 and at 1023 chains against the oracle."""
+    from tests.test_gpu_parity import _oracle_cfg
+    monkeypatch.delenv("RH_GRAD_WALK", raising=False)
+    monkeypatch.delenv("RH_LANES", raising=False)
+    spec = models.linreg(n=1_000_000, k=3)
+    m = R.Model(spec, device=0, fp_contract=True, factor_outputs=True)                      # bench.py's build
+    assert "#define RH_FP_CONTRACT 1" in m.hip_source
+    cfg = R.make_config(2, 0, R.HMCSampler(32), R.StaticStepSize(2e-4), R.IdentityMassMatrixTuner(), engine=_capi.ENGINE_TICK)
+    seeds = [1000 + c for c in range(1024)]                                                 # bench.py's seeds
+
+    def run(chains=1024):
+        s = R.Sampler(m, cfg, seeds[:chains]); s.warmup(); s.run(2)
+        out = (s.draws(), s.timing()["dominant_kernel"], [st.leapfrogSteps for st in s.stats()[0]])
+        s.close()
+        return out
+    auto = run()
+    assert auto[1] == "rh_grad_lane_kernel" and len(auto[2]) == 1024 and all(n == 64 for n in auto[2])
+    for c in (0, 1023):
+        want, _, _ = O.sample_model(spec, _oracle_cfg(cfg, O.JM_DET), seeds[c])
+        np.testing.assert_allclose(auto[0][c], want, rtol=1e-9, atol=1e-11, err_msg="the lane walk at 1e6 x 1024 differs from the ORACLE (chain %d)" % c)
+    for lanes in ("1", "2"):
+        monkeypatch.setenv("RH_LANES", lanes)
+        forced = run()
+        assert forced[1] == "rh_grad_lane_kernel" and forced[2] == auto[2]
+        assert np.array_equal(forced[0], auto[0]), "RH_LANES=%s changes the chains" % lanes
+    monkeypatch.delenv("RH_LANES")
+    assert run(512)[1] == "rh_grad_lane_kernel"
+    assert run(511)[1] == "rh_grad_fused_kernel"
+    monkeypatch.setenv("RH_GRAD_WALK", "lane")
+    rng = np.random.default_rng(22)
+    distinct = np.concatenate([rng.normal(size=(30, 5)) * 0.6,                              # the 32 points of the tile walk's test
+                               [[np.log(0.7), 0.5, 1.0, -2.0, 0.5]],
+                               [[0.0, 0.0, 0.0, 0.0, 0.0]]])
+    for chains in (1024, 1023):
+        worst = _check_tiled(spec, m, distinct, chains, chains, TOL_BIG, "cfg2-lane-%d" % chains)
+        print("cfg2 lane walk, %d chains: worst |got - ref| / (1e-11 * sum |term|) = %.3g" % (chains, worst))
+    m.close()
 
 
 @pytest.fixture(scope="module")

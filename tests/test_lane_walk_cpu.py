@@ -3,12 +3,14 @@ to the model's), which models get one, and the rule that picks the walk for a sa
 lane_nsplit), called through a tiny host library like tests/test_lanes_plan_cpu.py does."""
 import ctypes as C
 import os
+import re
 import subprocess
 import tempfile
 
 import pytest
 
 from rainier_amd import _capi, models
+from tests import lane_walk_cases as LC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rainier_amd", "csrc")
@@ -101,7 +103,8 @@ def test_the_rule_that_picks_the_walk():
     assert not is_lane(True, True, 8, 1024)          # an explicit K is a request for the tile kernel
     assert not is_lane(False, True, 0, 1024) and not is_lane(False, True, 0, 1024, forced=2)
     assert is_lane(True, False, 8, 1, rows=10, forced=2) and not is_lane(True, True, 0, 1024, forced=1)
-    # every sampler the GPU tests create has fewer than 512 chains in all, or an explicit K, or a dynamic sampler: the tile walk
+    # every sampler the GPU tests create has fewer than 512 chains in all, or an explicit K, or a dynamic sampler: the tile walk --
+    # but for the benched configuration's own test (tests/test_gpu_baseline_sizes.py), where the rule picks the walk on the device
     for chains in (1, 3, 9, 11, 21, 37, 64, 165, 256, 511):
         for k in (0, 2, 4, 8):
             for static in (False, True):
@@ -119,3 +122,78 @@ def test_row_splits_of_the_lane_walk():
         for rows in (1, 4096, 65_573, 1_000_000, 10_000_000):
             n = L.lw_nsplit(chains, rows)
             assert n >= 8 and n % 8 == 0
+
+
+# ---- which models get the walk (tests/lane_walk_cases.py): the cross-compile report of every case, with the case's data ----
+LANE = "rh_grad_lane_kernel"
+_reports = {}
+
+
+def _report(name, spec, opts):
+    if name not in _reports:
+        _reports[name] = _capi.lower_report(spec.rir, _capi.compile_opts(**opts), columns=spec.columns, nrows=spec.nrows)
+    return _reports[name]
+
+
+def _check_lane_entry(k, src):
+    """a lane kernel the engine keeps: fit, no spill, no scratch, and the static LDS of the workgroup's sums -- W wavefronts x C chains
+    per lane x RH_NACC_MAX sums x 64 lanes of doubles; -> (rows per scalar request, RH_NACC_MAX)"""
+    assert k["fit"] and k["vgpr_spills"] == 0 and k["sgpr_spills"] == 0 and k["scratch"] == 0 and k["unproven"] == 0
+    assert 0 < k["vgprs"] <= 256          # (__launch_bounds__(512): eight wavefronts on four SIMDs)
+    nacc_max = int(re.search(r"#define RH_NACC_MAX (\d+)", src).group(1))
+    assert k["lds"] == 8 * 2 * nacc_max * 64 * 8 <= 65536
+    return k["lane_r"], nacc_max
+
+
+@pytest.mark.parametrize("case", LC.CASES, ids=repr)
+def test_which_models_get_a_lane_kernel_and_with_how_many_rows_per_request(case):
+    """lane_eligible() / build_lane_code() decide silently, and RH_GRAD_WALK=lane falls back to the tile walk for a model without the
+    kernel: this is the test that notices a model losing, or gaining, the walk"""
+    spec = case.make(case.n_build)[0]
+    src, rep = _report(case.name, spec, case.opts)
+    lane = _lane(rep)
+    if not case.lane:
+        assert not lane, (case, lane)
+        return
+    assert list(lane) == [LANE], (case, "no lane kernel")
+    r, nacc_max = _check_lane_entry(lane[LANE], src)
+    assert r == case.r
+    assert nacc_max == {"linreg5-strict": 8, "linreg6-fast": 8}.get(case.name, nacc_max)      # the 64 KB of static LDS ...
+    if nacc_max == 8:
+        assert lane[LANE]["lds"] == 65536                                                     # ... exactly
+    assert ("HAS_VALUE_ONLY = true" in src) == case.value_only
+    assert int(re.search(r"#define RH_NROWTARGETS (\d+)", src).group(1)) == case.targets
+    if case.targets == 2:     # a target that adds fewer sums than the other: its own NA under the stride RH_NACC_MAX (in three of the four)
+        nacc = tuple(int(x) for x in re.findall(r"NACC = (\d+), ROWT = [01];", src))
+        assert nacc == {"two_targets-fast": (3, 2), "two_targets-strict": (4, 2), "two_targets_log-fast": (2, 2), "two_targets_log-strict": (2, 3)}[case.name]
+        assert max(nacc) == nacc_max
+
+
+def _source(spec, opts):
+    src = _capi.lower_only(spec.rir, _capi.compile_opts(**opts), columns=spec.columns, nrows=spec.nrows, compile=False)[0]
+    return src.split("\n// rh_kpool")[0]      # (the constant pool's values travel behind the source as a comment: not hashed)
+
+
+@pytest.mark.parametrize("case", LC.POSITIVE, ids=repr)
+def test_the_cases_source_does_not_depend_on_the_row_count(case):
+    # ... so that every row count tests/test_gpu_lane_walk_models.py runs loads the code objects build() left in the kernel cache
+    base = _source(case.make(case.n_build)[0], case.opts)
+    for n in tuple(case.row_counts) + (case.n_main,):
+        assert _source(case.make(n)[0], case.opts) == base, (case, n)
+
+
+def test_which_random_models_get_a_lane_kernel():
+    """tests/fuzz_models.GPU_FUZZ_CASES' eight-slot models, lowered with their data like build() does: LC.FUZZ_LANE lists exactly the
+    (seed, build) pairs with a lane kernel, so tests/test_gpu_lane_walk_models.py leaves out none that has one"""
+    have = []
+    for seed, kw in LC.FUZZ_SLOTS:
+        spec = LC.fuzz_spec(seed, kw)[0]
+        for build in ("fast", "strict"):
+            src, rep = _report("fuzz_slots_%d-%s" % (seed, build), spec, LC.BUILDS[build])
+            lane = _lane(rep)
+            if lane:
+                _check_lane_entry(lane[LANE], src)
+                have.append((seed, build))
+    assert sorted(have) == sorted(LC.FUZZ_LANE)
+    # (seed 1 has none in either build: its fast row code spills vector registers at 8 rows per request and scalar ones at 4)
+    assert {(0, "fast"), (2, "fast"), (3, "fast"), (2, "strict")} <= set(have) and not {(1, "fast"), (1, "strict")} & set(have)
