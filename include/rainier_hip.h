@@ -267,6 +267,9 @@ int rh_sampler_timing(rh_sampler *s, rh_timing *out, int reset);
  * sampler/Driver.scala:7-11, sampler/Progress.scala): how far the chains of this handle have been driven.
  * warmed: 1 once the warm-up phase is complete; iterations_done: sampling iterations completed (of cfg.iterations). */
 int rh_sampler_progress(const rh_sampler *s, int32_t *warmed, int32_t *iterations_done);
+/* the feed of the sampler's gradient launches: 0 = not the lane walk, 1 = the lane walk over the model's columns, 2 = over the
+   interleaved copy of the columns (csrc/device/rh_lane.hip.h); negative = error */
+int rh_sampler_lane_feed(const rh_sampler *s);
 
 /* ---- after the path: Generator.prepare / Trace.predict (next-row f3) -----------------------------------------------
  * The reference compiles a generator's `requirements` with Compiler.default.compile(parameters, namedReqs) and evaluates

@@ -28,7 +28,7 @@ EXPORTS = [
     "rh_model_engines", "rh_compile_count",
     "rh_density_eval", "rh_density_eval_ex", "rh_config_default", "rh_sample", "rh_sample_multi", "rh_sampler_create", "rh_sampler_destroy",
     "rh_sampler_warmup", "rh_sampler_run", "rh_sampler_draws", "rh_sampler_draws_device", "rh_sampler_stats",
-    "rh_sampler_timing", "rh_sampler_progress", "rh_sampler_mass_dense", "rh_optimize", "rh_diagnostics", "rh_sampler_diagnostics", "rh_diagnostics_device", "rh_abi_version", "rh_device_count", "rh_requirements_eval",
+    "rh_sampler_timing", "rh_sampler_progress", "rh_sampler_lane_feed", "rh_sampler_mass_dense", "rh_optimize", "rh_diagnostics", "rh_sampler_diagnostics", "rh_diagnostics_device", "rh_abi_version", "rh_device_count", "rh_requirements_eval",
     "rh_comm_unique_id", "rh_comm_create", "rh_comm_destroy", "rh_comm_allgather_draws", "rh_comm_allreduce_max", "rh_device_synchronize",
     # Trace.predict / Trace.thin over device-resident draws (core/Trace.scala:23-41, core/Generator.scala:59-94)
     "rh_predict_create", "rh_predict_destroy", "rh_predict_nreq", "rh_predict_nvars", "rh_sampler_predict", "rh_predict_device",

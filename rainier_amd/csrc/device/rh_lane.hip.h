@@ -15,6 +15,20 @@
 // accumulator set; the W wavefronts' sums go through LDS and are added in ascending w; one store per (split, chain, sum) into the
 // partial-sum layout of rh_grad_kernel.  A chain's bits depend on nsplit, W and R only -- not on the live count, the slot, the lane,
 // the other chains or the shards.  Only loads are scalar; every store is a vector store.
+//
+// ---- the two feeds -----------------------------------------------------------------------------------------------------------------
+// The COLUMN feed (rh_grad_lane_kernel) reads the model's columns as they are: a request is R rows of ONE column, so every column's
+// request must have arrived before the first row can start, and the R x NC values fill the 64 scalar registers there are for them --
+// a wavefront has nothing in flight while it computes, and only its SIMD's other wavefronts hide its requests' latency.
+// The ROW feed (this file compiled with RH_LANE_FEED_ROWS 1: rh_grad_lane_kernel of a code object of its own, engine.cpp
+// build_lane_rows_code) reads an interleaved copy of a target's columns -- element (r, j) at r NC + j, zeros up to a whole block of 8
+// rows, made once per model and device by the engine (ensure_lane_rows; lanes_plan.hpp lane_rows_*), its address a launch argument
+// (struct rh_lane_rows), rh_model_data untouched.  A 64-byte request is then whole rows; a SET is min(R, 16 / NC) rows = at most two
+// requests = 32 scalar registers, and there are two sets: while the pipe works on one, the other is on its way (wait for this set,
+// request the next, the rows of this set, swap).  For targets of 1, 2, 4 or 8 columns; any other target of the model walks its columns
+// as above.  Same grid, same split / piece arithmetic in blocks of R rows, same LDS reduction and stores, and the same rows in the same
+// order through the same rh_row into one accumulator set per chain: a chain's sums are the column feed's BIT FOR BIT
+// (tests/test_gpu_lane_feed.py), and SUMMATION ORDER above holds for both.  Measured on cfg 2: profiles/lane_feed_cfg2.
 #if RH_NROWTARGETS > 0 && !RH_HAS_GATHER && !RH_BIGTH && !RH_BIGN && !RH_LK_LDS
 #ifndef RH_LANE_W
 #define RH_LANE_W 8
@@ -25,9 +39,31 @@
 #ifndef RH_LANE_C
 #define RH_LANE_C 2
 #endif
+#ifndef RH_LANE_FEED_ROWS
+#define RH_LANE_FEED_ROWS 0
+#endif
 typedef const double __attribute__((address_space(4))) *rh_ccol_t;
+struct rh_lane_rows { const double *p[RH_NROWTARGETS]; };   // the interleaved copy of every row target (ROWT order; nullptr: none)
+// does a target of NC columns take its rows from the interleaved copy (lanes_plan.hpp lane_rows_eligible), and in sets of how many
+constexpr bool rh_lane_rowfed(int nc) { return RH_LANE_FEED_ROWS && (nc == 1 || nc == 2 || nc == 4 || nc == 8); }
+constexpr int rh_lane_set(int nc) { return 16 / nc < RH_LANE_R ? 16 / nc : RH_LANE_R; }
+// one set of S rows x NC columns, 64 or 128 bytes in whole aligned lines, from the interleaved copy into scalar registers
+template <int S, int NC> RH_DEV void rh_lane_request(double (&c)[S][NC], rh_ccol_t rp, const long long row) {
+#pragma unroll
+  for (int u = 0; u < S; u++)
+#pragma unroll
+    for (int j = 0; j < NC; j++) c[u][j] = rp[(row + u) * NC + j];
+}
+// "wait for this set": an empty statement that reads the set's registers, so that the wait for its requests stands HERE -- ahead of the
+// next set's requests (scalar loads return out of order: a wait further down would be for both sets)
+template <int S, int NC> RH_DEV void rh_lane_arrived(const double (&c)[S][NC]) {
+#pragma unroll
+  for (int u = 0; u < S; u++)
+#pragma unroll
+    for (int j = 0; j < NC; j++) asm volatile("" ::"s"(c[u][j]));
+}
 template <int T, bool NV>   // NV: the log-density is needed (row()); otherwise row_g()
-RH_DEV void rh_lane_targets(const double (&th)[RH_LANE_C][RH_NTH], const rh_model_data &d, const int w, const int split, const int nsplit,
+RH_DEV void rh_lane_targets(const double (&th)[RH_LANE_C][RH_NTH], const rh_model_data &d, const rh_lane_rows *rows, const int w, const int split, const int nsplit,
                             const int *__restrict__ lp, const int nvalid, const int chains, double *__restrict__ partial,
                             double *red, int &err) {
   if constexpr (T < RH_NTARGETS) {
@@ -56,6 +92,44 @@ RH_DEV void rh_lane_targets(const double (&th)[RH_LANE_C][RH_NTH], const rh_mode
 #pragma unroll
         for (int o = 0; o < NA; o++) acc[k][o] = 0.0;
       long long kb = r0;   // wave-uniform: the loops branch on scalars, the row code runs with all lanes active
+      if constexpr (rh_lane_rowfed(NC)) {
+        // THE ROW FEED: sets of S whole rows from the interleaved copy, two register sets; a set is requested one compute phase ahead
+        // (wait for A, request B, rows of A; wait for B, request A, rows of B).  The sets go in pairs, so that every request is used
+        // further down the same path and stays where it is written; an odd last set has been requested by the pair before it, and a
+        // request with no set behind it asks for the piece's last set again (a hit, never past the copy) and is dropped.  Same rows,
+        // same order, same rh_row as the column feed.
+        constexpr int S = rh_lane_set(NC);
+        static_assert(R % S == 0 && S * NC * 2 * 2 <= 64, "two sets of whole rows in 64 scalar registers, a block of R rows in whole sets");
+        const rh_ccol_t rp = (rh_ccol_t)rows->p[TG::ROWT];
+        const int nsets = (int)((r1 - kb) / S);
+        const long long last = kb + (long long)(nsets > 0 ? nsets - 1 : 0) * S;
+        auto rows_of = [&](const double (&cur)[S][NC]) {
+#pragma unroll
+          for (int u = 0; u < S; u++)
+#pragma unroll
+            for (int k = 0; k < C; k++) rh_row<TG, NV>(th[k], inv[k], cur[u], acc[k], err);
+        };
+        double ca[S][NC], cb[S][NC];
+        if (nsets > 0) rh_lane_request<S, NC>(ca, rp, kb);
+        for (int i = 0; i + 2 <= nsets; i += 2) {
+          rh_lane_arrived<S, NC>(ca);
+          rh_lane_request<S, NC>(cb, rp, kb + S);
+          __builtin_amdgcn_sched_barrier(0);   // (the requests stay ahead of the arithmetic)
+          rows_of(ca);
+          rh_lane_arrived<S, NC>(cb);
+          rh_lane_request<S, NC>(ca, rp, kb + 2 * S <= last ? kb + 2 * S : last);
+          __builtin_amdgcn_sched_barrier(0);
+          rows_of(cb);
+          kb += 2 * S;
+        }
+        if (nsets & 1) { rows_of(ca); kb += S; }
+        for (; kb < r1; kb++) {   // the ragged end of the last split: single rows, one request each
+          double c[1][NC];
+          rh_lane_request<1, NC>(c, rp, kb);
+#pragma unroll
+          for (int k = 0; k < C; k++) rh_row<TG, NV>(th[k], inv[k], c[0], acc[k], err);
+        }
+      } else {
       for (; kb + R <= r1; kb += R) {
         double c[R][NC];
 #pragma unroll
@@ -74,6 +148,7 @@ RH_DEV void rh_lane_targets(const double (&th)[RH_LANE_C][RH_NTH], const rh_mode
 #pragma unroll
         for (int k = 0; k < C; k++) rh_row<TG, NV>(th[k], inv[k], c, acc[k], err);
       }
+      }
 #pragma unroll
       for (int k = 0; k < C; k++)
 #pragma unroll
@@ -90,15 +165,13 @@ RH_DEV void rh_lane_targets(const double (&th)[RH_LANE_C][RH_NTH], const rh_mode
       }
       __syncthreads();   // (the next row target's sums go through the same buffer)
     }
-    rh_lane_targets<T + 1, NV>(th, d, w, split, nsplit, lp, nvalid, chains, partial, red, err);
+    rh_lane_targets<T + 1, NV>(th, d, rows, w, split, nsplit, lp, nvalid, chains, partial, red, err);
   }
 }
 // grid: ngroups * nsplit workgroups of W wavefronts, ngroups = ceil(chains / (64 C)); the XCD mapping of rh_grad_kernel
-extern "C" __global__ void __launch_bounds__(64 * RH_LANE_W)
-rh_grad_lane_kernel(const rh_model_data d, const double *__restrict__ q, const int *__restrict__ list, const int *__restrict__ nlive,
-                    const int *__restrict__ vflag, double *__restrict__ partial, int *__restrict__ err_out, int *__restrict__ n_running,
-                    const int chains, const int nsplit, const int xcd_aware) {
-  __shared__ double red[RH_LANE_W * RH_LANE_C * RH_NACC_MAX * 64];
+RH_DEV void rh_grad_lane_body(const rh_model_data &d, const rh_lane_rows *rows, const double *__restrict__ q, const int *__restrict__ list,
+                              const int *__restrict__ nlive, const int *__restrict__ vflag, double *__restrict__ partial, int *__restrict__ err_out,
+                              int *__restrict__ n_running, const int chains, const int nsplit, const int xcd_aware, double *red) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int b = blockIdx.x;
   if (b == 0 && threadIdx.x == 0) *n_running = 0; // re-armed for the tick kernel that follows in stream order
@@ -118,10 +191,29 @@ rh_grad_lane_kernel(const rh_model_data d, const double *__restrict__ q, const i
   }
   int err = 0;
   if constexpr (rh_any_value_only<0>::v) {
-    if (__all(gonly)) rh_lane_targets<0, false>(th, d, w, split, nsplit, list + slot0, nl - slot0, chains, partial, red, err);
-    else rh_lane_targets<0, true>(th, d, w, split, nsplit, list + slot0, nl - slot0, chains, partial, red, err);
+    if (__all(gonly)) rh_lane_targets<0, false>(th, d, rows, w, split, nsplit, list + slot0, nl - slot0, chains, partial, red, err);
+    else rh_lane_targets<0, true>(th, d, rows, w, split, nsplit, list + slot0, nl - slot0, chains, partial, red, err);
   } else
-  rh_lane_targets<0, true>(th, d, w, split, nsplit, list + slot0, nl - slot0, chains, partial, red, err);
+  rh_lane_targets<0, true>(th, d, rows, w, split, nsplit, list + slot0, nl - slot0, chains, partial, red, err);
   if (__any(err != 0) && lane == 0) atomicOr(err_out, 1);
 }
+#if !RH_LANE_FEED_ROWS
+extern "C" __global__ void __launch_bounds__(64 * RH_LANE_W)
+rh_grad_lane_kernel(const rh_model_data d, const double *__restrict__ q, const int *__restrict__ list, const int *__restrict__ nlive,
+                    const int *__restrict__ vflag, double *__restrict__ partial, int *__restrict__ err_out, int *__restrict__ n_running,
+                    const int chains, const int nsplit, const int xcd_aware) {
+  __shared__ double red[RH_LANE_W * RH_LANE_C * RH_NACC_MAX * 64];
+  rh_grad_lane_body(d, nullptr, q, list, nlive, vflag, partial, err_out, n_running, chains, nsplit, xcd_aware, red);
+}
+#else
+// the same launch with the rows fed from the interleaved copies: a code object of its own (engine.cpp build_lane_rows_code) and the
+// same name in it -- a sampler's timing names rh_grad_lane_kernel whichever feed its launches take (rh_sampler_lane_feed says which)
+extern "C" __global__ void __launch_bounds__(64 * RH_LANE_W)
+rh_grad_lane_kernel(const rh_model_data d, const rh_lane_rows rows, const double *__restrict__ q, const int *__restrict__ list,
+                    const int *__restrict__ nlive, const int *__restrict__ vflag, double *__restrict__ partial, int *__restrict__ err_out,
+                    int *__restrict__ n_running, const int chains, const int nsplit, const int xcd_aware) {
+  __shared__ double red[RH_LANE_W * RH_LANE_C * RH_NACC_MAX * 64];
+  rh_grad_lane_body(d, &rows, q, list, nlive, vflag, partial, err_out, n_running, chains, nsplit, xcd_aware, red);
+}
+#endif
 #endif

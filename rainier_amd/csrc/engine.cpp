@@ -158,6 +158,16 @@ struct rh_model {
   int grad_chains_req = 0;               // rh_compile_opts.grad_chains as the caller gave it (0 = automatic)
   bool lane_tried = false;               // build_lane_code has run (lane_code is final)
   int lane_r = 0;                        // rows per scalar request of the kernel in lane_code (8 or 4; 0: none)
+  // the lane walk's row feed (rh_grad_lane_kernel of a second code object: the same walk, the rows from an interleaved copy of each target's columns,
+  // lanes_plan.hpp): one more code object, empty / nullptr when no row target is eligible or the kernel is not fit to run
+  std::vector<char> lane_rows_code;
+  std::string lane_rows_why;             // why the model has lane_code but no lane_rows_code (empty: no target is eligible)
+  hipModule_t lane_rows_module = nullptr;
+  hipFunction_t k_grad_lane_rows = nullptr;
+  bool lane_rows_tried = false;          // build_lane_rows_code has run (lane_rows_code is final)
+  std::vector<void *> dev_rows;          // per row target (ROWT order) the interleaved copy on the device, or nullptr (made by ensure_lane_rows)
+  std::vector<long long> dev_rows_n;     // ... and the rows it holds: a launch whose data.nrows asks for more takes the column feed
+  std::vector<long long> rows_uploaded;  // per target the rows of its columns as uploaded (data.nrows may be a prefix for a while: selfcheck_density)
   int ncols_max = 0, glm_ncols = 0;
   hipFunction_t k_grad_glm = nullptr;
   bool glm_small = false;  // <= 8 predictors: the plain VALU kernel (the fp64 matrix pipe pays from ~9 predictors on, profiles/r1_c)
@@ -251,6 +261,7 @@ struct rh_sampler {
   void *d_rec[2] = {nullptr, nullptr};  // fused launches: the two record buffers (alternating)
   bool fuse = false;  // static HMC on the plain gradient kernel: mid-trajectory updates run as the gradient launch's epilogue
   bool lane_walk = false;          // the gradient launches are rh_grad_lane_kernel's (lanes_plan.hpp walk_is_lane; fixed at creation)
+  bool lane_rows = false;          // ... the row-fed rh_grad_lane_kernel's: the lane walk fed from the interleaved copies (feed_is_rows; fixed at creation)
   std::vector<Lane> lanes;         // one, or two halves of the chains on two streams (lanes_plan.hpp)
   std::vector<rh_chain_stats_dev> last_stats;
   int64_t grads_at_reset = 0;
@@ -663,6 +674,106 @@ hipFunction_t ensure_lane(rh_model *m) {
   HIPCHK(hipModuleLoadData(&m->lane_module, m->lane_code.data()));
   m->k_grad_lane = fit_kernel(m->lane_code, m->lane_module, "rh_grad_lane_kernel", nullptr);
   return m->k_grad_lane;
+}
+
+// The row feed's code object: the lane walk's translation unit with RH_LANE_FEED_ROWS in front (rh_grad_lane_kernel in its row-fed
+// form), at the rows per block the column feed settled on -- the two cut the rows alike, so a chain's sums are the same
+// bits.  Kept under the column feed's conditions, and only if it keeps the eight wavefronts per SIMD where the column feed has them.
+bool lane_rows_any_target(const rh_model *m) {
+  for (const auto &T : m->prog.targets) if (T.n_cols && rh_plan::lane_rows_eligible((int)T.n_cols, m->lane_r)) return true;
+  return false;
+}
+void build_lane_rows_code(rh_model *m) {
+  const char *K = "rh_grad_lane_kernel";   // (the row-fed entry point has the column-fed one's name, in a code object of its own)
+  m->lane_rows_code.clear();
+  m->lane_rows_why.clear();
+  m->lane_rows_tried = true;
+  if (m->lane_code.empty() || !lane_rows_any_target(m)) return;
+  const char *e = rh::knob("RH_HIPRTC_EXTRA");
+  const std::string extra = e ? e : "";
+  const bool cache = !std::getenv("RH_NO_KERNEL_CACHE");
+  const std::string src = "#define RH_LANE_FEED_ROWS 1\n" + (m->lane_r == rh_plan::kLaneR ? std::string() : "#define RH_LANE_R " + std::to_string(m->lane_r) + "\n") +
+                          m->source + "\n" + kLaneSrc;
+  // (the marker has the form of build_code's: the unfit kernels; the reason, for the build report, lies in a file of its own beside it)
+  const std::string marker = cache_path(m->arch, src, extra) + ".lanerows.unfit", reason = cache_path(m->arch, src, extra) + ".lanerows.why";
+  std::vector<char> mk;
+  if (cache && read_file(marker, mk) && std::string(mk.begin(), mk.end()).compare(0, marker_header().size(), marker_header()) == 0) {
+    m->lane_rows_why = read_file(reason, mk) ? std::string(mk.begin(), mk.end()) : "unfit";
+    return;
+  }
+  bool fit = false;
+  std::string why;
+  rh::KernelMeta km, kc;
+  std::vector<char> code;
+  try {
+    code = build_source(m->arch, src, extra, ".lanerows.co");
+    fit = kernel_health(code, K, &why) == KH_OK && rh::kernel_meta(code, K, km);
+    if (fit && (km.vgpr_spills != 0 || km.sgpr_spills != 0 || km.scratch_bytes != 0 || rh::kernel_touches_scratch(code, K) != 0)) { fit = false; why = "spills or scratch"; }
+    if (fit && rh::kernel_meta(m->lane_code, "rh_grad_lane_kernel", kc) && kc.vgprs <= 64 && km.vgprs > 64) {
+      fit = false; why = std::to_string(km.vgprs) + " vector registers where the column feed has " + std::to_string(kc.vgprs) + ": eight wavefronts per SIMD would be lost";
+    }
+  } catch (const Fail &f) { why = f.msg; }
+  if (rh::knob("RH_BUILD_LOG"))
+    std::fprintf(stderr, "[rh build] lane walk row feed R %d: vgprs %ld sgprs %ld spills %ld/%ld scratch %ld: %s %s\n", m->lane_r, km.vgprs, km.sgprs, km.vgpr_spills,
+                 km.sgpr_spills, km.scratch_bytes, fit ? "fit" : "unfit", why.c_str());
+  if (fit) { m->lane_rows_code = code; return; }
+  m->lane_rows_why = why.empty() ? "unfit" : why;
+  if (cache) {
+    std::remove((cache_path(m->arch, src, extra) + ".lanerows.co").c_str());
+    const std::string text = marker_header() + "\n" + K + "\n";
+    write_file(reason, std::vector<char>(m->lane_rows_why.begin(), m->lane_rows_why.end()));
+    write_file(marker, std::vector<char>(text.begin(), text.end()));
+  }
+}
+// The row feed's kernel and the interleaved copies it reads, made the first time a sampler or an evaluation could take it -- once per
+// model and device, rows x NC x 8 bytes per eligible target -- (nullptr: the model has none)
+hipFunction_t ensure_lane_rows(rh_model *m) {
+  std::lock_guard<std::recursive_mutex> lk(m->engine_mu);
+  if (m->k_grad_lane_rows) return m->k_grad_lane_rows;
+  if (!ensure_lane(m)) return nullptr;
+  if (!m->lane_rows_tried) build_lane_rows_code(m);
+  if (m->lane_rows_code.empty() || m->lane_rows_module) return nullptr;
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipModuleLoadData(&m->lane_rows_module, m->lane_rows_code.data()));
+  hipFunction_t k = fit_kernel(m->lane_rows_code, m->lane_rows_module, "rh_grad_lane_kernel", nullptr);
+  if (!k) return nullptr;
+  // The copies hold ALL the rows of the uploaded columns (rows_uploaded), whatever prefix data.nrows names at the moment -- the
+  // create-time self-check evaluates prefixes and may be the first to come here.  One column at a time goes through the host.  The
+  // copies are optional: where one cannot be made (no memory) the model has no row feed and its launches take the column feed.
+  m->dev_rows.assign((size_t)m->n_row_targets, nullptr);
+  m->dev_rows_n.assign((size_t)m->n_row_targets, 0);
+  try {
+    size_t c = 0, rowt = 0;
+    for (size_t t = 0; t < m->prog.targets.size(); t++) {
+      const int nc = (int)m->prog.targets[t].n_cols;
+      if (!nc) continue;
+      if (rh_plan::lane_rows_eligible(nc, m->lane_r)) {
+        const long long rows = t < m->rows_uploaded.size() ? m->rows_uploaded[t] : 0;
+        std::vector<double> col((size_t)rows), inter((size_t)rh_plan::lane_rows_doubles(rows, nc), 0.0);
+        for (int j = 0; j < nc; j++) {
+          if (rows) HIPCHK(hipMemcpy(col.data(), m->dev_cols[c + (size_t)j], sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost));
+          rh_plan::lane_rows_place_column(col.data(), rows, nc, j, inter.data());
+        }
+        void *d = nullptr;   // (hipMalloc's addresses are aligned to far more than a 64-byte line)
+        HIPCHK(hipMalloc(&d, std::max<size_t>(64, inter.size() * sizeof(double))));
+        m->dev_rows[rowt] = d;
+        m->dev_rows_n[rowt] = rows;
+        if (!inter.empty()) HIPCHK(hipMemcpy(d, inter.data(), inter.size() * sizeof(double), hipMemcpyHostToDevice));
+      }
+      c += (size_t)nc; rowt++;
+    }
+  } catch (const Fail &) {
+    (void)hipGetLastError();
+    for (void *d : m->dev_rows) if (d) (void)hipFree(d);
+    m->dev_rows.clear(); m->dev_rows_n.clear();
+    return nullptr;   // (lane_rows_module stays loaded: not tried again)
+  } catch (const std::bad_alloc &) {
+    for (void *d : m->dev_rows) if (d) (void)hipFree(d);
+    m->dev_rows.clear(); m->dev_rows_n.clear();
+    return nullptr;
+  }
+  m->k_grad_lane_rows = k;
+  return k;
 }
 
 // kernel `name` of `module` if it is fit to run (kernel_health); otherwise nullptr and the reason
@@ -1132,6 +1243,7 @@ extern "C" int rh_model_create(const void *rir, size_t rir_len, const double *co
     for (size_t t = 0; t < m->prog.targets.size(); t++) {
       const auto &T = m->prog.targets[t];
       m->data.nrows[t] = T.n_cols ? nrows_t[t] : 0;
+      m->rows_uploaded.push_back(m->data.nrows[t]);
       if (!T.n_cols) continue;
       m->rows_total += nrows_t[t];
       const int64_t nr = nrows_t[t];
@@ -1232,7 +1344,7 @@ extern "C" int rh_model_clone(const rh_model *src, int32_t device, rh_model **ou
     m->source = src->source; m->nacc_max = src->nacc_max; m->grad_k = src->grad_k; m->has_glm = src->has_glm;
     m->glm_small = src->glm_small; m->glm_w = src->glm_w; m->lk_lds = src->lk_lds; m->gather_waves = src->gather_waves;
     m->goff_host = src->goff_host; m->gather_count = src->gather_count; m->col_len = src->col_len; m->col_src = src->col_src;
-    m->rows_total = src->rows_total; m->data = src->data; m->data.cols = nullptr;
+    m->rows_total = src->rows_total; m->data = src->data; m->data.cols = nullptr; m->rows_uploaded = src->rows_uploaded;
     // ... and the state of the lowering itself: build_code / build_variant_code decide from it which kernels the model needs and
     // how the shape may still be lightened (a clone whose n_row_targets_hint stayed 0 accepted a variant with an unfit tick kernel)
     m->n_row_targets_hint = src->n_row_targets_hint; m->rows_unroll_auto = src->rows_unroll_auto; m->unroll_auto = src->unroll_auto;
@@ -1240,7 +1352,8 @@ extern "C" int rh_model_clone(const rh_model *src, int32_t device, rh_model **ou
     m->device = dev;
     m->arch = device_arch(dev);
     m->grad_chains_req = src->grad_chains_req;
-    if (m->arch == src->arch) { m->code = src->code; m->lane_code = src->lane_code; m->lane_r = src->lane_r; m->lane_tried = src->lane_tried; }
+    if (m->arch == src->arch) { m->code = src->code; m->lane_code = src->lane_code; m->lane_r = src->lane_r; m->lane_tried = src->lane_tried;
+      m->lane_rows_code = src->lane_rows_code; m->lane_rows_why = src->lane_rows_why; m->lane_rows_tried = src->lane_rows_tried; }   // (its interleaved copies: ensure_lane_rows, on its device)
     else build_code(m);   // (a mixed node: compiled or fetched from the cache for that architecture)
     load_module(m);
     if (m->want_nuts) (void)load_variant(m, 1);
@@ -1284,6 +1397,8 @@ extern "C" void rh_model_destroy(rh_model *m) {
     if (m->stream) hipStreamDestroy(m->stream);
     for (int v = 1; v < 8; v++)  // [0] aliases the base module
       if (m->variants[v].module && m->variants[v].module != m->module) hipModuleUnload(m->variants[v].module);
+    for (void *d : m->dev_rows) if (d) hipFree(d);
+    if (m->lane_rows_module) hipModuleUnload(m->lane_rows_module);
     if (m->lane_module) hipModuleUnload(m->lane_module);
     if (m->module) hipModuleUnload(m->module);
   }
@@ -1393,6 +1508,7 @@ extern "C" int rh_lower_report_data(const void *rir, size_t rir_len, const doubl
     if (code_size) {          // (nullptr: source only -- the CPU suite's host emulation of the generated code)
       build_code(&m);         // may lower again with a smaller row-loop unroll: the source returned is the one that was compiled
       build_lane_code(&m);
+      build_lane_rows_code(&m);
       *code_size = m.code.size();
     }
     if (src_out) {
@@ -1424,6 +1540,17 @@ extern "C" int rh_lower_report_data(const void *rir, size_t rir_len, const doubl
         std::istringstream all(code_report(m.lane_code, "lane"));
         for (std::string ln; std::getline(all, ln);)
           if (ln.find("rh_grad_lane_kernel") != std::string::npos) r += ln + " lane_r=" + std::to_string(m.lane_r) + " lds=" + std::to_string(km.lds_bytes) + "\n";
+      }
+      if (!m.lane_rows_code.empty()) {   // (the row feed's code object likewise, under a tag of its own)
+        rh::KernelMeta km;
+        rh::kernel_meta(m.lane_rows_code, "rh_grad_lane_kernel", km);
+        std::istringstream all(code_report(m.lane_rows_code, "lane_rows"));
+        for (std::string ln; std::getline(all, ln);)
+          if (ln.find("rh_grad_lane_kernel") != std::string::npos) r += ln + " lane_r=" + std::to_string(m.lane_r) + " lds=" + std::to_string(km.lds_bytes) + "\n";
+      } else if (!m.lane_rows_why.empty()) {   // eligible, built and dropped: the reason
+        std::string why = m.lane_rows_why;
+        std::replace(why.begin(), why.end(), '\n', ' ');
+        r += "lane_rows kernel=rh_grad_lane_kernel unproven=0 vgprs=0 sgprs=0 vgpr_spills=0 sgpr_spills=0 scratch=0 fit=0 lane_r=" + std::to_string(m.lane_r) + " lds=0 why=" + why + "\n";
       }
       *report = (char *)std::malloc(r.size() + 1); std::memcpy(*report, r.c_str(), r.size() + 1);
     }
@@ -1588,6 +1715,14 @@ bool walk_is_lane(rh_model *m, bool static_hmc, int total_chains) {
 int lane_nsplit(const rh_model *m, int total_chains) {
   return rh_plan::lane_nsplit(total_chains, lane_max_rows(m));
 }
+// the feed of a lane walk's launches: RH_LANE_FEED=cols|rows (RH_DIAG) forces it; `rows` is the column feed where the model has no
+// row-fed kernel.  The two feeds give a chain the same bits, so every shard decides for itself.
+bool feed_is_rows(rh_model *m) {
+  int forced = 0;
+  if (const char *e = rh::knob("RH_LANE_FEED")) forced = std::strcmp(e, "cols") == 0 ? 1 : (std::strcmp(e, "rows") == 0 ? 2 : 0);
+  if (!rh_plan::feed_is_rows(true, forced)) return false;   // (no reason to build the kernel and the copies)
+  return rh_plan::feed_is_rows(ensure_lane_rows(m) != nullptr, forced);
+}
 
 // one batched gradient launch of the tick engine: whichever row-streaming kernel the model was lowered to
 // (rh_grad_gather_kernel [+ rh_grad_gather_scan_kernel] | rh_grad_glm_kernel | rh_grad_kernel), per-split partial sums -> d_partial.
@@ -1595,11 +1730,22 @@ int lane_nsplit(const rh_model *m, int total_chains) {
 // workgroups of the slots past the live count -- the last of the grid -- return at once.
 // d_vflag: the chains' request flags (rh_tick_kernel: 2 = gradient only, the log-density of that evaluation is never read) or nullptr.
 void launch_grad(rh_model *m, GatherBufs *gb, void *d_q, void *d_list, void *d_nlive, void *d_vflag, void *d_partial, void *d_graderr, void *d_running,
-                 int chains, int nsplit, int xcd, hipStream_t stream = nullptr, bool lane_walk = false) {
+                 int chains, int nsplit, int xcd, hipStream_t stream = nullptr, bool lane_walk = false, bool lane_rows = false) {
   if (!stream) stream = m->stream;
   if (lane_walk) {   // rh_grad_lane_kernel: 64 C chains per group, W wavefronts per workgroup, rh_grad_kernel's arguments
-    void *la[] = {&m->data, &d_q, &d_list, &d_nlive, &d_vflag, &d_partial, &d_graderr, &d_running, &chains, &nsplit, &xcd};
     const int lgroups = (chains + rh_plan::kLaneGroup - 1) / rh_plan::kLaneGroup;
+    // (a copy holds the rows that were uploaded; should data.nrows ever name more, the launch takes the column feed: the same bits)
+    if (lane_rows) {
+      std::vector<long long> want;
+      for (size_t t = 0; t < m->prog.targets.size(); t++) if (m->prog.targets[t].n_cols) want.push_back(m->data.nrows[t]);
+      lane_rows = m->k_grad_lane_rows && rh_plan::lane_rows_cover((int)want.size(), want.data(), (int)m->dev_rows_n.size(), m->dev_rows_n.data(), m->dev_rows.data());
+    }
+    if (lane_rows) {   // the row-fed rh_grad_lane_kernel: the same, with the interleaved copies' addresses (struct rh_lane_rows) behind the model's data
+      void *ra[] = {&m->data, m->dev_rows.data(), &d_q, &d_list, &d_nlive, &d_vflag, &d_partial, &d_graderr, &d_running, &chains, &nsplit, &xcd};
+      launch(m->k_grad_lane_rows, (unsigned)(lgroups * nsplit), 64 * rh_plan::kLaneW, stream, ra);
+      return;
+    }
+    void *la[] = {&m->data, &d_q, &d_list, &d_nlive, &d_vflag, &d_partial, &d_graderr, &d_running, &chains, &nsplit, &xcd};
     launch(m->k_grad_lane, (unsigned)(lgroups * nsplit), 64 * rh_plan::kLaneW, stream, la);
     return;
   }
@@ -1656,6 +1802,7 @@ extern "C" int rh_density_eval_ex(rh_model *m, const double *q, int32_t chains, 
       // per-split partial sums (and, in gather mode, the scatter sums) for all chains, the finish kernel combines them in
       // the same fixed order as rh_tick_kernel (rh_combine_chain) -- so parity tests reach the kernels the bench times
       const bool lane_walk = walk_is_lane(m, false, chains);   // (only where RH_GRAD_WALK=lane asks for it)
+      const bool lane_rows = lane_walk && feed_is_rows(m);
       int nsplit = grad_splits > 0 ? grad_splits : (m->info.gather_mode ? 64 : lane_walk ? lane_nsplit(m, chains) : default_nsplit(m, chains));
       GatherBufs gb;
       if (m->info.gather_mode) gb.build(m, chains, nsplit);
@@ -1686,7 +1833,7 @@ extern "C" int rh_density_eval_ex(rh_model *m, const double *q, int32_t chains, 
           dnl = bnl->p;
         }
       }
-      launch_grad(m, &gb, dq, blist.p, dnl, nullptr, bpart.p, de, brun.p, chains, nsplit, xcd, nullptr, lane_walk);
+      launch_grad(m, &gb, dq, blist.p, dnl, nullptr, bpart.p, de, brun.p, chains, nsplit, xcd, nullptr, lane_walk, lane_rows);
       void *dpart = bpart.p;
       if (m->info.gather_mode) {
         void *fa[] = {&m->data, &gb.gd, &dq, &dpart, &dl, &dg, &de, &ch, &nsplit, &dtot};
@@ -1908,6 +2055,7 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
       // (each workgroup would combine 64 C chains x nsplit partial sums in its prologue, nsplit^2 x chains sums per launch: more
       // bytes than the rows), so its trajectories run launch, tick, launch.
       s->lane_walk = walk_is_lane(m, cfg->sampler == RH_SAMPLER_HMC, g_total_chains > 0 ? g_total_chains : chains);
+      s->lane_rows = s->lane_walk && feed_is_rows(m);
       int nsplit = cfg->grad_splits;
       if (nsplit <= 0) nsplit = s->lane_walk ? lane_nsplit(m, g_total_chains > 0 ? g_total_chains : chains) : default_nsplit(m, chains);
       // The dynamic samplers' trajectories end at different launches (EHMC: DefaultConfig's, sampler/Sampler.scala:17-27; NUTS:
@@ -2053,7 +2201,7 @@ void advance_to_ticks(rh_sampler *s, int it_stop) {
   };
   auto grad = [&](Lane &L, void *partial) {
     launch_grad(m, L.gb, L.qbuf, L.d_list, s->compact ? L.d_nlive : nullptr /* (without compaction d_list stays the identity) */,
-                value_free ? L.active : nullptr, partial, L.d_graderr, L.d_running, L.chains, nsplit, xcd, L.stream, s->lane_walk);
+                value_free ? L.active : nullptr, partial, L.d_graderr, L.d_running, L.chains, nsplit, xcd, L.stream, s->lane_walk, s->lane_rows);
   };
   // gradient at the point the PREVIOUS launch's gradient moves every chain to (rh_fused_prologue); no tick between the two
   auto grad_fused = [&](Lane &L, void *partial_in, void *partial_out, void *rec_in, void *rec_out) {
@@ -2363,6 +2511,11 @@ extern "C" int rh_sampler_geometry_(rh_sampler *s, int *device, void **stream, i
 }
 extern "C" void rh_set_thread_error_(const char *msg) { g_err = msg ? msg : ""; }
 
+// which feed the sampler's gradient launches take: 0 = they are not the lane walk's, 1 = the model's columns, 2 = the interleaved copy
+extern "C" int rh_sampler_lane_feed(const rh_sampler *s) {
+  if (!s) { g_err = "rh_sampler_lane_feed: NULL"; return -RH_E_INVALID; }
+  return !s->lane_walk ? 0 : (s->lane_rows ? 2 : 1);
+}
 extern "C" int rh_sampler_progress(const rh_sampler *s, int32_t *warmed, int32_t *iterations_done) {
   if (!s) { g_err = "rh_sampler_progress: NULL"; return RH_E_INVALID; }
   if (warmed) *warmed = s->warmed ? 1 : 0;

@@ -65,6 +65,44 @@ inline int lane_nsplit(int total_chains, long long max_rows) {
   return (int)std::min(nsplit, cap);
 }
 
+// ---- the lane walk's row feed (rh_grad_lane_kernel of the *.lanerows.co) ----
+// The same walk with the rows of a target taken from an interleaved copy of its columns -- element (r, j) of rows x NC at r NC + j,
+// zeros up to a whole block of 8 rows, base aligned to a 64-byte line -- so that one 64-byte request is whole rows and a SET of rows
+// can be asked for while the set before it is worked on.  A target takes the feed when its rows are 8, 16, 32 or 64 bytes:
+//   rows per set = min(rows per block, 16 / NC), at most 128 bytes = two requests = 32 scalar registers; two sets are the 64 the
+//   column feed holds; the set divides the block, so a piece of whole blocks is whole sets.
+inline int lane_rows_set(int nc, int r = kLaneR) { return nc >= 1 && nc <= 16 ? std::min(r, 16 / nc) : 0; }
+inline bool lane_rows_eligible(int nc, int r = kLaneR) {
+  if (!(nc == 1 || nc == 2 || nc == 4 || nc == 8)) return false;
+  const int set = lane_rows_set(nc, r);
+  return set >= 1 && 2 * set * nc * 2 <= 64 && r % set == 0 && 8 % set == 0;
+}
+inline long long lane_rows_padded(long long rows) { return (rows + 7) / 8 * 8; }              // rows of the copy, padding included
+inline long long lane_rows_doubles(long long rows, int nc) { return lane_rows_padded(rows) * nc; }
+inline long long lane_rows_index(long long r, int nc, int j) { return r * nc + j; }
+// out: lane_rows_doubles(rows, nc) doubles; cols: the target's nc columns of `rows` values
+inline void lane_rows_place_column(const double *col, long long rows, int nc, int j, double *out) {   // (the padding is the caller's)
+  for (long long r = 0; r < rows; r++) out[lane_rows_index(r, nc, j)] = col[r];
+}
+inline void lane_rows_interleave(const double *const *cols, long long rows, int nc, double *out) {
+  for (int j = 0; j < nc; j++) lane_rows_place_column(cols[j], rows, nc, j, out);
+  for (long long i = rows * nc, e = lane_rows_doubles(rows, nc); i < e; i++) out[i] = 0.0;
+}
+// May a launch whose row targets have want[i] rows read the copies -- have[i] rows each, copy[i] == nullptr where target i walks its
+// columns --?  Only if every copy holds at least the rows the launch walks (the kernel reads rows below want[i] and nothing else).
+inline bool lane_rows_cover(int n_want, const long long *want, int n_have, const long long *have, const void *const *copy) {
+  if (n_want != n_have) return false;
+  for (int i = 0; i < n_want; i++) if (copy[i] && want[i] > have[i]) return false;
+  return true;
+}
+// Which feed a sampler's lane-walk launches take: the row feed wherever the model has the kernel -- measured on cfg 2,
+// profiles/lane_feed_cfg2 --; forced: 0 = this rule, 1 = columns, 2 = rows wherever the kernel exists (RH_LANE_FEED).
+constexpr bool kLaneFeedRowsDefault = true;
+inline bool feed_is_rows(bool model_has_rows_kernel, int forced) {
+  if (!model_has_rows_kernel || forced == 1) return false;
+  return forced == 2 || kLaneFeedRowsDefault;
+}
+
 // ---- the busy share of overlapping spans ----
 // n spans [t0[i], t1[i]] on one time base (t1 < t0 is read as an empty span at t0).  share[i] = the integral over span i of
 // 1 / (spans open at that instant); the shares add up to the length of the union of the spans, which is the value returned.

@@ -739,6 +739,12 @@ class Sampler:
         _capi.check(_capi.lib().rh_sampler_mass_dense(self._h, _capi.dptr(out)), self.model._h)
         return out
 
+    def lane_feed(self):
+        """which feed the gradient launches take: None (not the lane walk), "cols" or "rows" (csrc/device/rh_lane.hip.h)"""
+        f = _capi.lib().rh_sampler_lane_feed
+        f.argtypes, f.restype = [C.c_void_p], C.c_int
+        return {0: None, 1: "cols", 2: "rows"}[f(self._h)]
+
     def timing(self, reset: bool = False):
         t = _capi.Timing()
         _capi.check(_capi.lib().rh_sampler_timing(self._h, C.byref(t), int(reset)), self.model._h)
