@@ -41,7 +41,8 @@ extern "C" {
                              6: rh_timing.chain_slots / steady_* (the tick engine's gradient launches serve the live chains only);
                                 (still 6, additions only: rh_sampler_diagnostics, rh_diagnostics_device, rh_predict_*, rh_*_summary*, rh_generate_*,
                                  rh_sampler_generate, rh_sampler_covariance, rh_covariance_device, rh_covariance_lower_only,
-                                 rh_sampler_histogram, rh_histogram_device, rh_sampler_histogram2d, rh_histogram2d_device, rh_histogram_lower_only) */
+                                 rh_sampler_histogram, rh_histogram_device, rh_sampler_histogram2d, rh_histogram2d_device, rh_histogram_lower_only,
+                                 rh_sampler_rank_diagnostics, rh_rank_diagnostics_device, rh_rank_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -496,6 +497,47 @@ int rh_histogram2d_device(const void *dev_draws, int32_t device, int32_t chains,
 /* No device needed: the histogram kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_histogram_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- rank-normalised split R-hat, bulk ESS and tail ESS over device-resident draws ----------------------------------------------
+ * Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021), computed where the draws are (csrc/device/rh_rank.hip.h).  rh_diagnostics
+ * and rh_sampler_diagnostics keep the reference's numbers (an unsplit R-hat on the raw values, a variogram ESS cut at lag 99); these
+ * see what those cannot: a trend all chains share, a chain of another scale, a posterior without a variance.
+ * Input: draws [chains][iterations][nvars], the window [first, first + count) of every chain, count >= 4, no thinning; column k of
+ * the result is parameter cols[k] (duplicates allowed); cols == NULL: all nvars in order, and ncols must be 0 or nvars.
+ * Split: h = count / 2 (floored).  Sequence q = 2c is (c, first + i), q = 2c + 1 is (c, first + count - h + i), i = 0 .. h-1: an odd
+ * count leaves the middle draw out.  M = 2 chains sequences, S = M h values, flat index s = q h + i.
+ * Order and ranks: Double.compare's order (-0.0 before +0.0), the summaries' key order.  The average rank of y_s among the S values is
+ * r_s = (L_s + U_s + 1) / 2, L_s the number of values below it, U_s the number at or below it; z_s = Phi^-1((r_s - 3/8) / (S + 1/4)),
+ * Phi^-1 by Wichura's AS 241 (PPND16).
+ * Four series per column, each [M][h]: 1. z(y), the bulk series; 2. z(|y - med|), med = 0.5 sorted[S/2 - 1] + 0.5 sorted[S/2], the
+ * folded series, ranked among themselves; 3. I(y <= sorted[floor(0.05 S)]); 4. I(y <= sorted[floor(0.95 S)]).  The thresholds are
+ * order statistics (precis'), not interpolated quantiles: exact, and O(1/S) from the paper's.
+ * Estimator on a series u [M][h], L = min(h - 1, 255):
+ *   m_q = mean_i u[q][i];  g_q(t) = (1/h) sum_{i=0}^{h-1-t} (u[q][i] - m_q)(u[q][i+t] - m_q), t = 0 .. L, i ascending, one accumulator
+ *   g(t) = mean_q g_q(t);  W = g(0) h / (h-1);  B = sum_q (m_q - mean_q m_q)^2 / (M-1);  V = (h-1)/h W + B;  rhat = sqrt(V / W)
+ *   rho_0 = 1; rho_t = 1 - (W - g(t)) / V;  P_k = rho_2k + rho_2k+1, k = 0 .. K, K = (L-1)/2
+ *   tau = -1; prev = +inf; for k = 0 .. K: if !(P_k > 0) { tau += max(rho_2k, 0); stop }  P = min(P_k, prev); prev = P; tau += 2P
+ *   tau = max(tau, 1 / log10(S));  ess = S / tau;  truncated: the loop ran out of pairs without stopping
+ * Outputs [K] each, caller-allocated on the host, none NULL: rhat_bulk and ess_bulk of series 1, rhat_folded of series 2, ess_tail
+ * the smaller ESS of series 3 and 4 (NaN if either is NaN), truncated (int32) bit 0 bulk, bit 1 lower tail, bit 2 upper tail: where a
+ * bit is set that ESS is an upper bound (the lags stop at 255: lag t is thread t of the chain kernel; seen on chains that do not mix).
+ * NaN: a column whose window holds a NaN or an infinity gives NaN in all four (truncated 0), other columns are untouched; a series
+ * whose W is not > 0 (a constant column, an indicator that is constant over all S -- the upper one whenever S < 20) gives NaN.
+ * Deterministic: no floating-point atomics, every sum in an order that depends on the shape alone; a second call, a window and its
+ * copy, and any chunking of the columns give the same bits.
+ * The workspace (per column 32 S bytes and 8 M (L + 2)) is bounded by 128 MiB and walked in chunks of columns; a single column beyond
+ * it returns RH_E_UNSUPPORTED from the shape alone, before any launch.  A broken window, count < 4, an index outside [0, nvars),
+ * ncols < 1 with a list, a NULL output: RH_E_INVALID.  No device: RH_E_DEVICE (no CPU fallback).
+ * The sampler form goes to the sampler's stream behind its pending work, is not part of rh_timing and does not alter the chains. */
+int rh_sampler_rank_diagnostics(rh_sampler *s, int32_t first, int32_t count, const int32_t *cols, int32_t ncols, double *rhat_bulk,
+                                double *rhat_folded, double *ess_bulk, double *ess_tail, int32_t *truncated);
+/* the same over any device buffer [chains][iterations][nvars] on `device` (-1: the current one); synchronises the device before and after */
+int rh_rank_diagnostics_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                               int32_t count, const int32_t *cols, int32_t ncols, double *rhat_bulk, double *rhat_folded, double *ess_bulk,
+                               double *ess_tail, int32_t *truncated);
+/* No device needed: the rank diagnostics kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_rank_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */

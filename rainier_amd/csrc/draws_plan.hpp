@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -12,10 +12,12 @@
 #define RH_SUMMARY_HOST 1
 #define RH_COV_HOST 1
 #define RH_HIST_HOST 1
+#define RH_RANK_HOST 1
 #include "device/rh_trace.hip.h"
 #include "device/rh_summary.hip.h"
 #include "device/rh_cov.hip.h"
 #include "device/rh_hist.hip.h"
+#include "device/rh_rank.hip.h"
 // rh_generate.hip.h's routine needs the prelude's rng around it: the CPU test's driver defines RH_GENERATE_HOST with one in place
 #ifndef RH_GENERATE_HOST
 #define RG_CONSTANTS_ONLY 1
@@ -132,6 +134,39 @@ inline void histogram_edges(double lo, double hi, int nbins, double *e) {
   e[0] = lo;
   for (int i = 1; i < nbins; i++) e[i] = std::min(hi, std::max(e[i - 1], lo + ((double)i * w) / (double)nbins));
   e[nbins] = hi;
+}
+// ---- rank-normalised split R-hat, bulk and tail ESS (device/rh_rank.hip.h) ----
+struct Rank {
+  long long h, M, S;             // values of a half; sequences (2 per chain); values of one column
+  int L, sl;                     // lags 0 .. L of the bulk and tail series (min(h - 1, RK_MAXLAG)); doubles per (column, sequence) of ws: L + 2
+  long long per_col, pc;         // workspace bytes of one column (y, two key buffers, one series buffer, ws); columns per chunk
+  bool over_cap;                 // one column alone is beyond the cap
+  long long tiles, mtiles;       // tile sorts and merge workgroups per column: the summary's plan of one flat chain of S values
+  int passes;                    // merge passes; pass k merges runs of run(k) keys
+  long long stiles, blocks;      // stage tiles of RK_ROWS flat values; blocks of RK_BLOCK values of the per-value kernels
+  long long i05, i95;            // the tail thresholds' order statistics (precis: floor(S * q)), as summary_plan computes idx
+  double tau_min;                // 1 / log10(S)
+  long long run(int k) const { return (long long)RS_TILE << k; }
+};
+// K: the selected columns; cap: RK_WS_CAP_BYTES (a parameter for the CPU tests' driver, where small shapes make several chunks)
+inline Rank rank_plan(long long chains, long long count, long long K, long long cap = RK_WS_CAP_BYTES) {
+  Rank P = {};
+  P.h = count / 2;
+  P.M = 2 * chains;
+  P.S = P.M * P.h;
+  P.L = (int)std::min<long long>(P.h - 1, RK_MAXLAG);
+  P.sl = P.L + 2;
+  P.per_col = 4 * P.S * 8 + P.M * P.sl * 8;
+  P.over_cap = P.per_col > cap;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_col, K));
+  const double tails[2] = {0.05, 0.95};
+  const Summary Q = summary_plan(1, P.S, 1, 1, tails, 2, 0.0);
+  P.tiles = Q.tiles; P.mtiles = Q.mtiles; P.passes = Q.passes;
+  P.i05 = Q.idx[0]; P.i95 = Q.idx[1];
+  P.stiles = (P.S + RK_ROWS - 1) / RK_ROWS;
+  P.blocks = (P.S + RK_BLOCK - 1) / RK_BLOCK;
+  P.tau_min = 1.0 / std::log10((double)P.S);
+  return P;
 }
 // ---- predict (device/rh_predict.hip.h) ----
 // that header cannot be included without a generated program around it, so these four are mirrors: RP_WAVE, RP_MAX_TILE, RP_LDS_DOUBLES, RP_TILE_FOR

@@ -578,6 +578,45 @@ def _histogram2d_result(call, pairs, bins, rng, model=None):
     return Histogram2d(tuple((int(a), int(b)) for a, b in pr), xe, ye, grid, outside)
 
 
+class RankDiagnostics(NamedTuple):
+    """Rank-normalised split R-hat, bulk and tail ESS (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021) per selected column.
+    rhat = max(rhat_bulk, rhat_folded) (NaN where either is); truncated: bit 0 bulk, bit 1 lower tail, bit 2 upper tail -- where a bit
+    is set the lags ran out at 255 before the autocorrelations did and that ESS is an upper bound."""
+    rhat: np.ndarray
+    rhat_bulk: np.ndarray
+    rhat_folded: np.ndarray
+    ess_bulk: np.ndarray
+    ess_tail: np.ndarray
+    truncated: np.ndarray
+    cols: Tuple[int, ...]
+
+
+def _rank_result(call, nvars, cols, model=None):
+    """shared by Sampler.rank_diagnostics and rank_diagnostics_device: call(cols, ncols, rhat_bulk, rhat_folded, ess_bulk, ess_tail, truncated) -> rc"""
+    sel = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+    k = int(nvars) if sel is None else len(sel)
+    rb, rf, eb, et = (np.zeros(max(k, 1)) for _ in range(4))
+    tr = np.zeros(max(k, 1), dtype=np.int32)
+    buf = sel if sel is None or k else np.zeros(1, dtype=np.int32)       # an empty list is a list (refused), not "all columns"
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _capi.check(call(ip(buf) if sel is not None else None, k if sel is not None else 0, _capi.dptr(rb), _capi.dptr(rf), _capi.dptr(eb),
+                     _capi.dptr(et), ip(tr)), model)
+    rb, rf, eb, et, tr = rb[:k], rf[:k], eb[:k], et[:k], tr[:k]
+    rhat = np.where(np.isnan(rb) | np.isnan(rf), np.nan, np.maximum(rb, rf))
+    return RankDiagnostics(rhat, rb, rf, eb, et, tr, tuple(range(k)) if sel is None else tuple(sel.tolist()))
+
+
+def rank_diagnostics_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
+                            cols: Optional[Sequence[int]] = None) -> RankDiagnostics:
+    """Rank-normalised split R-hat, bulk ESS and tail ESS over the window [first, first + count) (count >= 4, each chain split in two
+    halves) of a device buffer [chains][iterations][nvars] (a sampler's draws, a predictor's to_host = False result,
+    Comm.allgather_draws(to_host=False)), computed where the draws are (rh_rank_diagnostics_device).  cols: the parameters asked for,
+    in the result's order (None: all).  diagnostics_device keeps the reference's unsplit R-hat and variogram ESS."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_rank_diagnostics_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count, *a)
+    return _rank_result(call, nvars, cols)
+
+
 def histogram_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
                      thin: int = 1, cols: Optional[Sequence[int]] = None, bins: int = 20, range=None) -> Histogram:
     """Histograms of the pooled kept iterations first + j * thin of a device buffer [chains][iterations][nvars] (a sampler's draws, a
@@ -731,6 +770,16 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_histogram2d(self._h, int(first), count, int(thin), *a)
         return _histogram2d_result(call, pairs, bins, range, self.model._h)
+
+    def rank_diagnostics(self, first: int = 0, count: Optional[int] = None, cols: Optional[Sequence[int]] = None) -> RankDiagnostics:
+        """Can this run be trusted: rank-normalised split R-hat, bulk ESS and tail ESS (Vehtari et al. 2021) of the parameters over
+        the window [first, first + count) of every chain, computed where the draws are (rh_sampler_rank_diagnostics).  It sees what
+        diagnostics() (the reference's unsplit R-hat on the raw values) cannot: a trend all chains share, a chain of another scale, a
+        posterior without a variance.  cols: the parameters asked for, in the result's order (None: all); count = None: everything
+        completed so far.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_rank_diagnostics(self._h, int(first), count, *a)
+        return _rank_result(call, self.model.nVars, cols, self.model._h)
 
     def mass_dense(self) -> np.ndarray:
         """DenseMassMatrix.elements of every chain: [chains][nVars][nVars] (DenseMassMatrixTuner only)."""
