@@ -42,7 +42,8 @@ extern "C" {
                                 (still 6, additions only: rh_sampler_diagnostics, rh_diagnostics_device, rh_predict_*, rh_*_summary*, rh_generate_*,
                                  rh_sampler_generate, rh_sampler_covariance, rh_covariance_device, rh_covariance_lower_only,
                                  rh_sampler_histogram, rh_histogram_device, rh_sampler_histogram2d, rh_histogram2d_device, rh_histogram_lower_only,
-                                 rh_sampler_rank_diagnostics, rh_rank_diagnostics_device, rh_rank_lower_only) */
+                                 rh_sampler_rank_diagnostics, rh_rank_diagnostics_device, rh_rank_lower_only,
+                                 rh_loo_device, rh_sampler_loo, rh_loo_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -538,6 +539,56 @@ int rh_rank_diagnostics_device(const void *dev_draws, int32_t device, int32_t ch
 /* No device needed: the rank diagnostics kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_rank_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- pointwise WAIC and PSIS-LOO over device-resident log-likelihood draws --------------------------------------------------------
+ * Which of two models predicts better (Vehtari, Gelman, Gabry 2017), computed where the draws are (csrc/device/rh_loo.hip.h).
+ * Input: ll [chains][iterations][nvars], column i holding l_s = log p(y_i | theta_s); the kept iterations first + j * thin of every
+ * chain, kept = ceil(count / thin) (rh_sampler_summary's window); one column has S = chains * kept pooled values, S >= 2.  Column k of
+ * the result is column cols[k] (duplicates allowed); cols == NULL: all nvars in order, and ncols must be 0 or nvars.
+ * WAIC per column:
+ *   lpd = max + log(sum_s exp(l_s - max)) - log(S);  p_waic = sum_s (l_s - mean)^2 / (S - 1), mean = sum_s l_s / S, in two passes
+ *   (elpd_waic = lpd - p_waic is the caller's).
+ * PSIS per column (Vehtari, Simpson, Gelman, Yao, Gabry, as the `loo` package computes it):
+ *   1. r_s = -l_s, sorted in the summaries' key order, r_(1) <= .. <= r_(S);  x = r - r_(S) <= 0.  (The device sorts l ascending and
+ *      reads it backwards: the same subtraction l_(1) - l, the same bits.)
+ *   2. M = ceil(min(S / 5, 3 sqrt(S))).
+ *   3. lc = max(x_(S - M), log DBL_MIN).
+ *   4. The tail: the n sorted values with x > lc (n <= M).  n <= 4: no smoothing, k = +inf.
+ *   5. t_j = exp(x_(S - n + j)) - exp(lc), j = 1 .. n, ascending.
+ *   6. Zhang & Stephens (2009): m = 30 + floor(sqrt(n));  b_j = [1 - sqrt(m / (j - 1/2))] / (3 t_(floor(n/4 + 1/2))) + 1 / t_(n), j = 1 .. m;
+ *      k_j = mean_i log1p(-b_j t_i) (i ascending, one accumulator);  L_j = n (log(-b_j / k_j) - k_j - 1);  w_j = exp(L_j - logsumexp L),
+ *      logsumexp L = max L + log(sum_j exp(L_j - max L)), no weight dropped;  bbar = sum_j b_j w_j;  khat = mean_i log1p(-bbar t_i);
+ *      sigma = -khat / bbar;  the reported and used k = (n khat + 5) / (n + 10).
+ *   7. p_j = (j - 1/2) / n;  q_j = sigma expm1(-k log1p(-p_j)) / k  (k == 0: -sigma log1p(-p_j));  the new log weight is
+ *      lw_j = min(log(q_j + exp(lc)), 0).
+ *   8. A k or a sigma that is not finite leaves the tail as it is and reports k = +inf.
+ *   9. elpd_loo = log(sum_s exp(l_s + lw_s)) - log(sum_s exp(lw_s)), lw = x outside the tail and the smoothed value inside; outside the
+ *      tail (and in a tail left as it is) l_s + lw_s = -r_(S) exactly, so it is evaluated as
+ *        -r_(S) + log((S - n) + sum_j exp(lw_j - x_j)) - log(sum_{outside} exp(x_s) + sum_j exp(lw_j))     (an unsmoothed tail: lw_j = x_j)
+ *      off the sorted column alone: no permutation is kept.
+ * Sums over a column: thread t of 256 adds the sorted values i = t, t + 256, .. in ascending i, then a fixed binary tree; the m
+ * weights are added in candidate order.  exp and log are fdlibm 5.3's, written out; log1p(x) = log(u) x / (u - 1) with u = fl(1 + x)
+ * (x where u == 1) and expm1(x) = (u - 1) x / log(u) with u = exp(x) (x where u == 1, -1 where u - 1 == -1).
+ * Outputs [K] each, caller-allocated on the host, none NULL: lpd, p_waic, elpd_loo, pareto_k, tail_n (int32, the n above).
+ * A column whose window holds a NaN or an infinity gives NaN in the four doubles and tail_n = 0; other columns are untouched.  A
+ * constant column gives p_waic = 0 (its mean is taken to be the value itself), k = +inf, tail_n = 0 and elpd_loo = lpd = l.
+ * Deterministic: no floating-point atomics, every sum in an order that depends on the shape alone; a second call, a window and its
+ * copy, any chunking of the columns and a shuffled column list give the same bits per column.
+ * The workspace (16 S bytes per column) is bounded by 128 MiB and walked in chunks of columns; a single column beyond it, and one
+ * whose M is beyond the 8064 tail values a workgroup's LDS holds (S above about 7.2 million), return RH_E_UNSUPPORTED from the shape
+ * alone, before any launch.  A broken window, S < 2, an index outside [0, nvars), ncols < 1 with a list, a NULL output: RH_E_INVALID.
+ * No device: RH_E_DEVICE (no CPU fallback).  Synchronises the device before and after. */
+int rh_loo_device(const void *dev_ll, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first, int32_t count,
+                  int32_t thin, const int32_t *cols, int32_t ncols, double *lpd, double *p_waic, double *elpd_loo, double *pareto_k,
+                  int32_t *tail_n);
+/* rh_sampler_predict's window through predictor p (whose requirements are the pointwise log-likelihoods), then the reduction above
+ * over p's buffer [chains][kept][nreq] (cols index its requirements) behind it on the sampler's stream: one synchronisation, nothing
+ * copied to the host but the figures.  Not part of rh_timing; the chains are not altered. */
+int rh_sampler_loo(rh_sampler *s, rh_predict *p, int32_t first, int32_t count, int32_t thin, const int32_t *cols, int32_t ncols, double *lpd,
+                   double *p_waic, double *elpd_loo, double *pareto_k, int32_t *tail_n);
+/* No device needed: the WAIC / PSIS-LOO kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_loo_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how long the tail of a PSIS column, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -13,11 +13,13 @@
 #define RH_COV_HOST 1
 #define RH_HIST_HOST 1
 #define RH_RANK_HOST 1
+#define RH_LOO_HOST 1
 #include "device/rh_trace.hip.h"
 #include "device/rh_summary.hip.h"
 #include "device/rh_cov.hip.h"
 #include "device/rh_hist.hip.h"
 #include "device/rh_rank.hip.h"
+#include "device/rh_loo.hip.h"
 // rh_generate.hip.h's routine needs the prelude's rng around it: the CPU test's driver defines RH_GENERATE_HOST with one in place
 #ifndef RH_GENERATE_HOST
 #define RG_CONSTANTS_ONLY 1
@@ -166,6 +168,30 @@ inline Rank rank_plan(long long chains, long long count, long long K, long long 
   P.stiles = (P.S + RK_ROWS - 1) / RK_ROWS;
   P.blocks = (P.S + RK_BLOCK - 1) / RK_BLOCK;
   P.tau_min = 1.0 / std::log10((double)P.S);
+  return P;
+}
+// ---- pointwise WAIC and PSIS-LOO (device/rh_loo.hip.h) ----
+struct Loo {
+  long long kept, S;             // kept iterations per chain; values of one pooled column
+  long long M, cut;              // the most tail values, ceil(min(S / 5, 3 sqrt(S))); the cutoff's order statistic x_(cut) of the ascending ratios, cut = S - M (1-based)
+  long long per_col, pc;         // workspace bytes of one column (the two key buffers); columns per chunk
+  bool over_cap, over_lds;       // one column alone is beyond the cap; M is beyond the tail's LDS (LL_TAIL_MAX)
+  long long tiles, mtiles;       // tile sorts and merge workgroups per column: the summary's plan
+  int passes;                    // merge passes; pass k merges runs of run(k) keys
+  long long run(int k) const { return (long long)RS_TILE << k; }
+};
+// K: the selected columns; cap: LL_WS_CAP_BYTES (a parameter for the CPU tests' driver, where small shapes make several chunks)
+inline Loo loo_plan(long long chains, long long count, long long thin, long long K, long long cap = LL_WS_CAP_BYTES) {
+  Loo P = {};
+  const Summary Q = summary_plan(chains, count, thin, 1, nullptr, 0, 0.0);
+  P.kept = Q.kept; P.S = Q.N;
+  P.tiles = Q.tiles; P.mtiles = Q.mtiles; P.passes = Q.passes;
+  P.M = (long long)std::ceil(std::min((double)P.S / 5.0, 3.0 * std::sqrt((double)P.S)));
+  P.cut = P.S - P.M;
+  P.per_col = 2 * P.S * (long long)sizeof(unsigned long long);
+  P.over_cap = P.per_col > cap;
+  P.over_lds = P.M > LL_TAIL_MAX;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_col, K));
   return P;
 }
 // ---- predict (device/rh_predict.hip.h) ----

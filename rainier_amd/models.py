@@ -219,6 +219,36 @@ def eight_schools_predict():
     return g.compile_requirements([mu + tau * g.param(2 + j) for j in range(8)]), 8
 
 
+def eight_schools_loglik():
+    """The pointwise log-likelihood of cfg 3 (bench/stan/EightSchools.scala): log Normal(y_j | theta_j, sigma_j), theta_j = mu + tau z_j,
+    over eight_schools()'s parameters (m, c, z_1..z_8), written as eight_schools() writes its eight likelihood targets -- what
+    Sampler.loo reduces to WAIC and PSIS-LOO.  (rir, n_requirements)"""
+    g = Graph(10, [])
+    mu, tau = g.param(0) * 5.0, (g.param(1) * 5.0).abs()
+    liks = []
+    for j, (y, sg) in enumerate(zip(EIGHT_SCHOOLS_Y, EIGHT_SCHOOLS_SIGMA)):
+        u = ((g.param(2 + j) * tau + mu) * -1.0 + y) / sg
+        liks.append(std_normal_logpdf(u) - math.log(sg))
+    return g.compile_requirements(liks), 8
+
+
+def linreg_loglik(k: int, x, y):
+    """The pointwise log-likelihood of cfg 2's regression on a small data set over linreg()'s parameters (s, a, b_0..b_{k-1}): one
+    requirement per row, log Normal(y_i | a + b . x_i, exp(s)), x [n][k] and y [n].  (rir, n_requirements)"""
+    x, y = np.asarray(x, dtype=np.float64).reshape(len(y), k), np.asarray(y, dtype=np.float64)
+    g = Graph(2 + k, [])
+    s = g.param(0)
+    inv_var = (s * -2.0).exp()
+    rows = []
+    for xi, yi in zip(x, y):
+        mu = g.param(1)
+        for j in range(k):
+            mu = mu + g.param(2 + j) * float(xi[j])
+        r = mu * -1.0 + float(yi)
+        rows.append((r * r) * inv_var / -2.0 - s - HALF_LOG_2PI)
+    return g.compile_requirements(rows), len(y)
+
+
 def lookup_predict(nvars: int = 4):
     """A prediction through a Lookup over parameters whose index -- the truncation of 2 * theta_0 -- leaves the table [0, nvars - 1)
     for some draws (RH_E_LOOKUP).  (rir, n_requirements)"""

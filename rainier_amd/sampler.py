@@ -617,6 +617,72 @@ def rank_diagnostics_device(ptr: int, chains: int, iterations: int, nvars: int, 
     return _rank_result(call, nvars, cols)
 
 
+class Loo(NamedTuple):
+    """Pointwise WAIC and PSIS-LOO (Vehtari, Gelman, Gabry 2017) per selected observation: lpd, p_waic, elpd_waic = lpd - p_waic,
+    elpd_loo, p_loo = lpd - elpd_loo, the Pareto shape pareto_k of the importance ratios' tail (above 0.7: that elpd_loo is not to be
+    trusted; +inf: a tail too short to fit) and its length tail_n.  A column with a NaN or an infinity is NaN."""
+    lpd: np.ndarray
+    p_waic: np.ndarray
+    elpd_waic: np.ndarray
+    elpd_loo: np.ndarray
+    p_loo: np.ndarray
+    pareto_k: np.ndarray
+    tail_n: np.ndarray
+    cols: Tuple[int, ...]
+
+    @staticmethod
+    def _total(pointwise):
+        n = len(pointwise)
+        return float(np.sum(pointwise)), float(np.sqrt(n * np.var(pointwise, ddof=1))) if n > 1 else float("nan")
+
+    def loo(self) -> Tuple[float, float]:
+        """(sum of elpd_loo, its standard error sqrt(n var(pointwise, ddof=1)))"""
+        return self._total(self.elpd_loo)
+
+    def waic(self) -> Tuple[float, float]:
+        """(sum of elpd_waic, its standard error)"""
+        return self._total(self.elpd_waic)
+
+    def p_loo_total(self) -> Tuple[float, float]:
+        """(the effective number of parameters sum of p_loo, its standard error)"""
+        return self._total(self.p_loo)
+
+    def p_waic_total(self) -> Tuple[float, float]:
+        """(sum of p_waic, its standard error)"""
+        return self._total(self.p_waic)
+
+
+def _loo_result(call, nvars, cols, model=None):
+    """shared by Sampler.loo and loo_device: call(cols, ncols, lpd, p_waic, elpd_loo, pareto_k, tail_n) -> rc"""
+    sel = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+    k = int(nvars) if sel is None else len(sel)
+    lpd, pw, el, pk = (np.zeros(max(k, 1)) for _ in range(4))
+    tn = np.zeros(max(k, 1), dtype=np.int32)
+    buf = sel if sel is None or k else np.zeros(1, dtype=np.int32)       # an empty list is a list (refused), not "all columns"
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _capi.check(call(ip(buf) if sel is not None else None, k if sel is not None else 0, _capi.dptr(lpd), _capi.dptr(pw), _capi.dptr(el),
+                     _capi.dptr(pk), ip(tn)), model)
+    lpd, pw, el, pk, tn = lpd[:k], pw[:k], el[:k], pk[:k], tn[:k]
+    return Loo(lpd, pw, lpd - pw, el, lpd - el, pk, tn, tuple(range(k)) if sel is None else tuple(sel.tolist()))
+
+
+def loo_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
+               thin: int = 1, cols: Optional[Sequence[int]] = None) -> Loo:
+    """Pointwise WAIC and PSIS-LOO over the kept iterations first + j * thin of a device buffer [chains][iterations][nvars] of
+    log-likelihoods, column i holding log p(y_i | theta_s) (a predictor's to_host = False result), computed where they are
+    (rh_loo_device): only five figures per observation return.  cols: the observations asked for, in the result's order (None: all)."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_loo_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count, int(thin), *a)
+    return _loo_result(call, nvars, cols)
+
+
+def loo_compare(a: Loo, b: Loo) -> Tuple[float, float]:
+    """(elpd_diff, se_diff) of model a against model b over the same observations: the sum of the pointwise differences of elpd_loo
+    (positive: a predicts better) and sqrt(n var(differences, ddof=1))."""
+    d = np.asarray(a.elpd_loo) - np.asarray(b.elpd_loo)
+    return float(np.sum(d)), float(np.sqrt(len(d) * np.var(d, ddof=1)))
+
+
 def histogram_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
                      thin: int = 1, cols: Optional[Sequence[int]] = None, bins: int = 20, range=None) -> Histogram:
     """Histograms of the pooled kept iterations first + j * thin of a device buffer [chains][iterations][nvars] (a sampler's draws, a
@@ -780,6 +846,15 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_rank_diagnostics(self._h, int(first), count, *a)
         return _rank_result(call, self.model.nVars, cols, self.model._h)
+
+    def loo(self, predictor: Predictor, first: int = 0, count: Optional[int] = None, thin: int = 1, cols: Optional[Sequence[int]] = None) -> Loo:
+        """Which model predicts better: pointwise WAIC and PSIS-LOO (Vehtari, Gelman, Gabry 2017) of the predictor's requirements --
+        the log-likelihood of every observation -- over the kept iterations first + j * thin of every chain.  The chains x kept x
+        observations matrix is made and reduced on the device (rh_sampler_loo) and never leaves it.  cols: the observations asked
+        for, in the result's order (None: all); count = None: everything completed so far.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_loo(self._h, predictor._h, int(first), count, int(thin), *a)
+        return _loo_result(call, predictor.nreq, cols, self.model._h)
 
     def mass_dense(self) -> np.ndarray:
         """DenseMassMatrix.elements of every chain: [chains][nVars][nVars] (DenseMassMatrixTuner only)."""
