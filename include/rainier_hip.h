@@ -43,7 +43,8 @@ extern "C" {
                                  rh_sampler_generate, rh_sampler_covariance, rh_covariance_device, rh_covariance_lower_only,
                                  rh_sampler_histogram, rh_histogram_device, rh_sampler_histogram2d, rh_histogram2d_device, rh_histogram_lower_only,
                                  rh_sampler_rank_diagnostics, rh_rank_diagnostics_device, rh_rank_lower_only,
-                                 rh_loo_device, rh_sampler_loo, rh_loo_lower_only) */
+                                 rh_loo_device, rh_sampler_loo, rh_loo_lower_only,
+                                 rh_loo_expect_device, rh_sampler_loo_expect, rh_loo_expect_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -589,6 +590,52 @@ int rh_sampler_loo(rh_sampler *s, rh_predict *p, int32_t first, int32_t count, i
 /* No device needed: the WAIC / PSIS-LOO kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_loo_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- PSIS leave-one-out expectations and LOO-PIT over device-resident draws ---------------------------------------------------------
+ * Is the model calibrated: the leave-one-out predictive distribution of each observation (the `loo` package's E_loo and loo_pit),
+ * computed where the draws are (csrc/device/rh_loo_expect.hip.h) with the smoothed importance weights rh_loo_device fits.
+ * Input: ll [chains][iterations][nll] (column i: l_s = log p(y_i | theta_s)) and val [chains][iterations][nval] (a prediction or a
+ * replicated observation per draw) on one device -- they may be one buffer -- over rh_loo_device's window and thinning; S = chains *
+ * kept >= 2 draws, flat index s = c * kept + j.  Result k pairs log-likelihood column ll_cols[k] with value column val_cols[k]; both
+ * lists are required, duplicates are allowed.  Per pair:
+ *   a. The tail fit: steps 1 - 8 of rh_loo_device on the log-likelihood column, bit for bit: pareto_k and tail_n are what rh_loo_device
+ *      returns for that column.
+ *   b. The weight of draw s.  a: the ascending sorted column, n the tail's length, [p_lo, p_hi) the positions whose key equals the key
+ *      of l_s (a group of equal keys lies wholly inside or wholly outside the tail, which is cut by value).  Outside the tail, or in a
+ *      tail left unsmoothed: W_s = exp(a[0] - l_s).  Inside a smoothed tail: W_s = (sum_{p = p_lo}^{p_hi - 1} exp(lw_{n - p})) / (p_hi -
+ *      p_lo), added in ascending p with one accumulator: draws with equal log-likelihoods (mostly rejected proposals, that is, repeated
+ *      draws) share their group's mean weight, which does not depend on the draws' order and keeps the total weight.  W_s <= 1.
+ *   c. Sums over s: thread t of 256 adds s = t, t + 256, .. in ascending order, then a fixed binary tree.  den = sum W;
+ *      mean = sum W v / den (where every draw has one value, that value itself, as rh_loo_device takes a constant column's mean: the
+ *      variance is then 0);  var = sum W (v - mean)^2 / den, in a second pass;  pit = sum W [v <= y_k] / den;  pit_lt the same with <
+ *      (a discrete y_rep is randomised between the two on the host);  ess = den^2 / sum W^2.
+ * y [ncols] or NULL: without it pit and pit_lt may be NULL and are not written; a NaN y[k] gives NaN in both; y = +inf gives exactly 1
+ * (the sums den runs, in den's order), y = -inf exactly 0.  Outputs [ncols] each, caller-allocated on the host: mean, var, pit,
+ * pit_lt, ess, pareto_k, tail_n (int32).
+ * A NaN or an infinity in the log-likelihood window gives NaN in all doubles and tail_n = 0, as in rh_loo_device; one in the value
+ * window gives NaN in mean, var, pit and pit_lt and leaves ess, pareto_k and tail_n intact.  A constant log-likelihood column gives k =
+ * +inf, n = 0 and W = 1: the plain mean and variance, ess = S.  Other pairs are never touched.
+ * Deterministic: no floating-point atomics, every sum in an order fixed by the shape; a second call, a window and its copy, any
+ * chunking and any order of the pair list give the same bits per pair.
+ * The workspace (per pair 16 S bytes, the two key buffers, of which the spare one then holds the draws' weights, and 8 M for the tail's
+ * weights) is bounded by 128 MiB and walked in chunks of pairs; a single pair beyond it, and one whose M is beyond the 8064 tail values a
+ * workgroup's LDS holds, return RH_E_UNSUPPORTED from the shape alone, before any launch.  A broken window, S < 2, an index out of
+ * range, ncols < 1, a NULL list or a NULL output (pit, pit_lt: with y): RH_E_INVALID; the two buffers on different devices:
+ * RH_E_INVALID.  No device: RH_E_DEVICE (no CPU fallback).  Synchronises the device before and after. */
+int rh_loo_expect_device(const void *dev_ll, int32_t nll, const void *dev_val, int32_t nval, int32_t device, int32_t chains, int32_t iterations,
+                         int32_t first, int32_t count, int32_t thin, const int32_t *ll_cols, const int32_t *val_cols, int32_t ncols, const double *y,
+                         double *mean, double *var, double *pit, double *pit_lt, double *ess, double *pareto_k, int32_t *tail_n);
+/* rh_sampler_predict's window through p_ll (the pointwise log-likelihoods) and p_val (they may be one predictor); with g (may be NULL),
+ * g runs over p_val's output exactly as rh_sampler_generate runs it with chain0 = 0 -- the same seed gives the same y_rep bits -- and
+ * the values are the generator's outputs, which val_cols then index.  The reduction above follows on the sampler's stream: one
+ * synchronisation, nothing copied to the host but the figures.  Not part of rh_timing; the chains are not altered.  p_ll, p_val and g
+ * on different devices, or g's width not p_val's: RH_E_INVALID. */
+int rh_sampler_loo_expect(rh_sampler *s, rh_predict *p_ll, rh_predict *p_val, rh_generate *g, int64_t seed, int32_t first, int32_t count,
+                          int32_t thin, const int32_t *ll_cols, const int32_t *val_cols, int32_t ncols, const double *y, double *mean,
+                          double *var, double *pit, double *pit_lt, double *ess, double *pareto_k, int32_t *tail_n);
+/* No device needed: the leave-one-out expectation kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as
+ * before a launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_loo_expect_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */

@@ -44,6 +44,7 @@ EXPORTS = [
     "rh_sampler_rank_diagnostics", "rh_rank_diagnostics_device", "rh_rank_lower_only",
     # pointwise WAIC and PSIS-LOO over device-resident log-likelihood draws (Vehtari, Gelman, Gabry 2017)
     "rh_loo_device", "rh_sampler_loo", "rh_loo_lower_only",
+    "rh_loo_expect_device", "rh_sampler_loo_expect", "rh_loo_expect_lower_only",
 ]
 # ... and the two whose names hold a digit, which that test's pattern of a declaration does not read (tests/test_histogram_device_cpu.py checks them)
 EXPORTS_2D = ["rh_sampler_histogram2d", "rh_histogram2d_device"]
@@ -171,6 +172,9 @@ def lib():
     L.rh_loo_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_sampler_loo.argtypes = [vp, vp, i32, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_loo_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_loo_expect_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, ip, ip, i32, dp, dp, dp, dp, dp, dp, dp, ip]
+    L.rh_sampler_loo_expect.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, i32, ip, ip, i32, dp, dp, dp, dp, dp, dp, dp, ip]
+    L.rh_loo_expect_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_comm_unique_id.argtypes = [C.c_char_p]
     L.rh_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.rh_comm_destroy.argtypes = [vp]
@@ -379,6 +383,19 @@ def loo_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_loo_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def loo_expect_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_loo_expect.hip.h behind rh_summary.hip.h and rh_loo.hip.h (PSIS leave-one-out expectations on the device) -> code
+    object for `arch`, without a device: compiled through the kernel cache and judged as before a launch (no spills, no scratch,
+    isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_loo_expect_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

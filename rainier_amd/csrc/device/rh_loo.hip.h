@@ -176,6 +176,82 @@ LL_FN double ll_expm1(const double x) {
 
 LL_FN bool ll_finite(const double v) { return v - v == 0.0; }
 
+// ---- the tail of one sorted column (steps 1 - 8 of the contract; rh_loo_expect.hip.h calls the same three routines) -------------------
+// s: the column's keys in ascending order, finite; a0 = a [0].  The cutoff lc = max(a [0] - a [M], log DBL_MIN), exp(lc), and the tail's
+// length n <= M: the values with x = a [0] - a [i] > lc (a binary search: x does not grow along a and x at M is not above lc)
+LL_FN int ll_tail_cut(const rs_key *s, const long long M, const double a0, double *elc) {
+  const double lc0 = a0 - rs_from_key(s[M]), lmin = ll_log(LL_DBL_MIN), lc = lc0 > lmin ? lc0 : lmin;
+  *elc = ll_exp(lc);
+  long long lo = 0, hi = M;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (a0 - rs_from_key(s[mid]) > lc) lo = mid + 1; else hi = mid;
+  }
+  return (int)lo;
+}
+
+// Zhang & Stephens' fit of the generalised Pareto distribution to the tail a [0 .. n), n > 4 (a block routine: every thread of the
+// workgroup calls it).  lds: LL_LDS_DOUBLES doubles, all of them overwritten.  -> whether the tail is smoothed; *kk, *sigma: the shape
+// (with the prior's weight) and the scale
+LL_FN bool ll_tail_fit(const rs_key *s, const int n, const double a0, const double elc, double *lds, double *kk, double *sigma, const int ll_nthreads) {
+  const int rs_nthreads = ll_nthreads;
+  (void)rs_nthreads;
+  double *tail = lds, *sa = lds + LL_TAIL_MAX, *sb = sa + LL_BLOCK, *sc = sb + LL_BLOCK;
+  const double dn = (double)n;
+  // t_j = exp(x_j) - exp(lc), j = 1 .. n ascending: tail [j - 1]
+  LL_EACH_THREAD(tid) {
+    for (int j = tid; j < n; j += LL_BLOCK) tail[j] = ll_exp(a0 - rs_from_key(s[n - 1 - j])) - elc;
+  }
+  LL_SYNC();
+  int m = (int)__builtin_sqrt(dn);
+  while (m * m > n) m--;
+  while ((m + 1) * (m + 1) <= n) m++;
+  m += 30;
+  const double tq = tail[(n + 2) / 4 - 1], tn = tail[n - 1];
+  LL_EACH_THREAD(tid) {
+    if (tid < m) {
+      const double b = (1.0 - __builtin_sqrt((double)m / ((double)(tid + 1) - 0.5))) / (3.0 * tq) + 1.0 / tn;
+      double acc = 0.0;
+      for (int i = 0; i < n; i++) acc += ll_log1p(-b * tail[i]);
+      const double kj = acc / dn;
+      sa[tid] = dn * (ll_log(-b / kj) - kj - 1.0);
+      sb[tid] = b;
+    }
+  }
+  LL_SYNC();
+  LL_EACH_THREAD(tid) {
+    if (tid == 0) {                             // the m weights in candidate order
+      double top = sa[0], se = 0.0, bb = 0.0;
+      for (int j = 1; j < m; j++) top = sa[j] > top ? sa[j] : top;
+      for (int j = 0; j < m; j++) se += ll_exp(sa[j] - top);
+      const double lse = top + ll_log(se);
+      for (int j = 0; j < m; j++) bb += sb[j] * ll_exp(sa[j] - lse);
+      sc[0] = bb;
+    }
+  }
+  LL_SYNC();
+  const double bbar = sc[0];
+  LL_EACH_THREAD(tid) {
+    double acc = 0.0;
+    for (int i = tid; i < n; i += LL_BLOCK) acc += ll_log1p(-bbar * tail[i]);
+    sa[tid] = acc;
+  }
+  rs_tree_sum(sa, rs_nthreads);
+  const double khat = sa[0] / dn;
+  *sigma = -khat / bbar;
+  *kk = (dn * khat + 5.0) / (dn + 10.0);
+  LL_SYNC();
+  return ll_finite(*kk) && ll_finite(*sigma);
+}
+
+// the smoothed log weight lw_j of the tail's j-th smallest ratio, j = 1 .. n: the fitted distribution's quantile at (j - 0.5) / n, not above 0
+LL_FN double ll_tail_lw(const int j, const int n, const double kk, const double sigma, const double elc) {
+  const double l1 = ll_log1p(-((double)j - 0.5) / (double)n);
+  const double q = kk == 0.0 ? -sigma * l1 : sigma * ll_expm1(-kk * l1) / kk;
+  const double v = ll_log(q + elc);
+  return v > 0.0 ? 0.0 : v;
+}
+
 // ---- one column -------------------------------------------------------------------------------------------------------------------------
 // s: the column's S keys in ascending order (a [i] = rs_from_key(s [i])); M = ceil(min(S / 5, 3 sqrt(S))) <= LL_TAIL_MAX, M < S.
 // lds: LL_LDS_DOUBLES doubles.  Evaluated as
@@ -187,7 +263,7 @@ LL_FN void ll_column_block(const rs_key *s, const long long S, const long long M
                            double *pareto_k, int *tail_n, const int ll_nthreads) {
   const int rs_nthreads = ll_nthreads;
   (void)rs_nthreads;
-  double *tail = lds, *sa = lds + LL_TAIL_MAX, *sb = sa + LL_BLOCK, *sc = sb + LL_BLOCK;
+  double *sa = lds + LL_TAIL_MAX, *sb = sa + LL_BLOCK, *sc = sb + LL_BLOCK;
   const double nan = rs_from_key(RS_KEY_NAN), inf = __builtin_huge_val();
   if (s[0] <= LL_KEY_NEG_INF || s[S - 1] >= LL_KEY_POS_INF) {       // a NaN or an infinity in the column
     LL_EACH_THREAD(tid) {
@@ -196,17 +272,8 @@ LL_FN void ll_column_block(const rs_key *s, const long long S, const long long M
     return;
   }
   const double a0 = rs_from_key(s[0]), mx = rs_from_key(s[S - 1]), dS = (double)S;
-  const double lc0 = a0 - rs_from_key(s[M]), lmin = ll_log(LL_DBL_MIN), lc = lc0 > lmin ? lc0 : lmin, elc = ll_exp(lc);
-  // the tail: a [0 .. n), the values with x > lc; x does not grow along a and x at M is not above lc
-  int n;
-  {
-    long long lo = 0, hi = M;
-    while (lo < hi) {
-      const long long mid = (lo + hi) >> 1;
-      if (a0 - rs_from_key(s[mid]) > lc) lo = mid + 1; else hi = mid;
-    }
-    n = (int)lo;
-  }
+  double elc;
+  const int n = ll_tail_cut(s, M, a0, &elc);
   LL_EACH_THREAD(tid) {
     double as = 0.0, ae = 0.0, ad = 0.0;
     for (long long i = tid; i < S; i += LL_BLOCK) {
@@ -243,62 +310,14 @@ LL_FN void ll_column_block(const rs_key *s, const long long S, const long long M
 
   double k = inf, kk = 0.0, sigma = 0.0;
   bool smooth = false;
-  if (n > 4) {
-    const double dn = (double)n;
-    // t_j = exp(x_j) - exp(lc), j = 1 .. n ascending: tail [j - 1]
-    LL_EACH_THREAD(tid) {
-      for (int j = tid; j < n; j += LL_BLOCK) tail[j] = ll_exp(a0 - rs_from_key(s[n - 1 - j])) - elc;
-    }
-    LL_SYNC();
-    int m = (int)__builtin_sqrt(dn);
-    while (m * m > n) m--;
-    while ((m + 1) * (m + 1) <= n) m++;
-    m += 30;
-    const double tq = tail[(n + 2) / 4 - 1], tn = tail[n - 1];
-    LL_EACH_THREAD(tid) {
-      if (tid < m) {
-        const double b = (1.0 - __builtin_sqrt((double)m / ((double)(tid + 1) - 0.5))) / (3.0 * tq) + 1.0 / tn;
-        double acc = 0.0;
-        for (int i = 0; i < n; i++) acc += ll_log1p(-b * tail[i]);
-        const double kj = acc / dn;
-        sa[tid] = dn * (ll_log(-b / kj) - kj - 1.0);
-        sb[tid] = b;
-      }
-    }
-    LL_SYNC();
-    LL_EACH_THREAD(tid) {
-      if (tid == 0) {                             // the m weights in candidate order
-        double top = sa[0], se = 0.0, bb = 0.0;
-        for (int j = 1; j < m; j++) top = sa[j] > top ? sa[j] : top;
-        for (int j = 0; j < m; j++) se += ll_exp(sa[j] - top);
-        const double lse = top + ll_log(se);
-        for (int j = 0; j < m; j++) bb += sb[j] * ll_exp(sa[j] - lse);
-        sc[0] = bb;
-      }
-    }
-    LL_SYNC();
-    const double bbar = sc[0];
-    LL_EACH_THREAD(tid) {
-      double acc = 0.0;
-      for (int i = tid; i < n; i += LL_BLOCK) acc += ll_log1p(-bbar * tail[i]);
-      sa[tid] = acc;
-    }
-    rs_tree_sum(sa, rs_nthreads);
-    const double khat = sa[0] / dn;
-    sigma = -khat / bbar;
-    kk = (dn * khat + 5.0) / (dn + 10.0);
-    smooth = ll_finite(kk) && ll_finite(sigma);
-    LL_SYNC();
-  }
+  if (n > 4) smooth = ll_tail_fit(s, n, a0, elc, lds, &kk, &sigma, ll_nthreads);
   // the tail's two sums: smoothed, or as it is
   LL_EACH_THREAD(tid) {
     double an = 0.0, ad = 0.0;
     for (int j = tid + 1; j <= n; j += LL_BLOCK) {
       const double x = a0 - rs_from_key(s[n - j]);
       if (smooth) {
-        const double l1 = ll_log1p(-((double)j - 0.5) / (double)n);
-        const double q = kk == 0.0 ? -sigma * l1 : sigma * ll_expm1(-kk * l1) / kk;
-        const double v = ll_log(q + elc), lw = v > 0.0 ? 0.0 : v;
+        const double lw = ll_tail_lw(j, n, kk, sigma, elc);
         an += ll_exp(lw - x);
         ad += ll_exp(lw);
       } else {

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how long the tail of a PSIS column, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -14,12 +14,14 @@
 #define RH_HIST_HOST 1
 #define RH_RANK_HOST 1
 #define RH_LOO_HOST 1
+#define RH_LOO_EXPECT_HOST 1
 #include "device/rh_trace.hip.h"
 #include "device/rh_summary.hip.h"
 #include "device/rh_cov.hip.h"
 #include "device/rh_hist.hip.h"
 #include "device/rh_rank.hip.h"
 #include "device/rh_loo.hip.h"
+#include "device/rh_loo_expect.hip.h"
 // rh_generate.hip.h's routine needs the prelude's rng around it: the CPU test's driver defines RH_GENERATE_HOST with one in place
 #ifndef RH_GENERATE_HOST
 #define RG_CONSTANTS_ONLY 1
@@ -192,6 +194,27 @@ inline Loo loo_plan(long long chains, long long count, long long thin, long long
   P.over_cap = P.per_col > cap;
   P.over_lds = P.M > LL_TAIL_MAX;
   P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_col, K));
+  return P;
+}
+// ---- PSIS leave-one-out expectations (device/rh_loo_expect.hip.h) ----
+struct LooExpect {
+  long long kept, S, M;          // as Loo's
+  long long per_pair, pc;        // workspace bytes of one pair (the two key buffers -- the spare one holds the draws' weights -- and the tail's weights [M]); pairs per chunk
+  bool over_cap, over_lds;       // one pair alone is beyond the cap; M is beyond the tail's LDS (LL_TAIL_MAX)
+  long long tiles, mtiles;       // tile sorts and merge workgroups per pair: the summary's plan
+  int passes;                    // merge passes; pass k merges runs of run(k) keys
+  long long run(int k) const { return (long long)RS_TILE << k; }
+};
+// K: the selected pairs; cap: LX_WS_CAP_BYTES (a parameter for the CPU tests' driver, where small shapes make several chunks)
+inline LooExpect loo_expect_plan(long long chains, long long count, long long thin, long long K, long long cap = LX_WS_CAP_BYTES) {
+  LooExpect P = {};
+  const Loo Q = loo_plan(chains, count, thin, 1, cap);
+  P.kept = Q.kept; P.S = Q.S; P.M = Q.M;
+  P.tiles = Q.tiles; P.mtiles = Q.mtiles; P.passes = Q.passes;
+  P.per_pair = LX_PAIR_BYTES(P.S, P.M);
+  P.over_cap = P.per_pair > cap;
+  P.over_lds = Q.over_lds;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, K));
   return P;
 }
 // ---- predict (device/rh_predict.hip.h) ----

@@ -249,6 +249,21 @@ def linreg_loglik(k: int, x, y):
     return g.compile_requirements(rows), len(y)
 
 
+def linreg_fitted(k: int, x):
+    """The fitted values of cfg 2's regression on the rows of linreg_loglik over linreg()'s parameters (s, a, b_0..b_{k-1}): one
+    requirement per row, a + b . x_i, and the noise scale exp(s) as the last -- what a Generator turns into replicated observations
+    for Sampler.loo_expect.  (rir, n_requirements)"""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, k)
+    g = Graph(2 + k, [])
+    rows = []
+    for xi in x:
+        mu = g.param(1)
+        for j in range(k):
+            mu = mu + g.param(2 + j) * float(xi[j])
+        rows.append(mu)
+    return g.compile_requirements(rows + [g.param(0).exp()]), len(x) + 1
+
+
 def lookup_predict(nvars: int = 4):
     """A prediction through a Lookup over parameters whose index -- the truncation of 2 * theta_0 -- leaves the table [0, nvars - 1)
     for some draws (RH_E_LOOKUP).  (rir, n_requirements)"""

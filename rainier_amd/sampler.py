@@ -683,6 +683,59 @@ def loo_compare(a: Loo, b: Loo) -> Tuple[float, float]:
     return float(np.sum(d)), float(np.sqrt(len(d) * np.var(d, ddof=1)))
 
 
+class LooExpect(NamedTuple):
+    """PSIS leave-one-out expectations per selected pair (log-likelihood column ll_cols[k], value column val_cols[k]): the mean and
+    variance of the leave-one-out predictive distribution of the value (the `loo` package's E_loo), the LOO probability integral
+    transform pit = P(value <= y | y_-i) and pit_lt (the same with <: a discrete y_rep is randomised between the two) -- None
+    without y --, the PSIS effective sample size ess, and the Pareto shape pareto_k and tail length tail_n that Loo reports for the
+    column (above 0.7: not to be trusted).  A NaN or an infinity among the log-likelihoods makes every figure of the pair NaN; one
+    among the values makes mean, var, pit and pit_lt NaN."""
+    mean: np.ndarray
+    var: np.ndarray
+    pit: Optional[np.ndarray]
+    pit_lt: Optional[np.ndarray]
+    ess: np.ndarray
+    pareto_k: np.ndarray
+    tail_n: np.ndarray
+    ll_cols: Tuple[int, ...]
+    val_cols: Tuple[int, ...]
+
+
+def _loo_expect_result(call, nll, nval, ll_cols, val_cols, y, model=None):
+    """shared by Sampler.loo_expect and loo_expect_device: call(ll_cols, val_cols, ncols, y, mean, var, pit, pit_lt, ess, pareto_k,
+    tail_n) -> rc; without lists column i is paired with column i up to the narrower width"""
+    both = range(max(0, min(int(nll), int(nval))))
+    lc = np.ascontiguousarray([int(c) for c in (both if ll_cols is None else ll_cols)], dtype=np.int32)
+    vc = np.ascontiguousarray([int(c) for c in (both if val_cols is None else val_cols)], dtype=np.int32)
+    if len(lc) != len(vc):
+        raise ValueError("loo_expect: ll_cols and val_cols pair up: %d against %d entries" % (len(lc), len(vc)))
+    k = len(lc)
+    yy = None if y is None else np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if yy is not None and len(yy) != k:
+        raise ValueError("loo_expect: y has %d entries for %d pairs" % (len(yy), k))
+    mean, var, pit, plt, ess, pk = (np.zeros(max(k, 1)) for _ in range(6))
+    tn = np.zeros(max(k, 1), dtype=np.int32)
+    ip = lambda a: (a if len(a) else np.zeros(1, dtype=np.int32)).ctypes.data_as(C.POINTER(C.c_int32))   # an empty list is a list (refused)
+    yp = None if yy is None else _capi.dptr(yy if k else np.zeros(1))
+    _capi.check(call(ip(lc), ip(vc), k, yp, _capi.dptr(mean), _capi.dptr(var), _capi.dptr(pit) if yy is not None else None,
+                     _capi.dptr(plt) if yy is not None else None, _capi.dptr(ess), _capi.dptr(pk), tn.ctypes.data_as(C.POINTER(C.c_int32))), model)
+    return LooExpect(mean[:k], var[:k], pit[:k] if yy is not None else None, plt[:k] if yy is not None else None, ess[:k], pk[:k], tn[:k],
+                     tuple(lc.tolist()), tuple(vc.tolist()))
+
+
+def loo_expect_device(ll_ptr: int, val_ptr: int, chains: int, iterations: int, nll: int, nval: int, ll_cols: Sequence[int],
+                      val_cols: Sequence[int], y: Optional[Sequence[float]] = None, device: int = 0, first: int = 0,
+                      count: Optional[int] = None, thin: int = 1) -> LooExpect:
+    """Is the model calibrated: PSIS leave-one-out expectations over the kept iterations first + j * thin of two buffers on one
+    device, log-likelihoods [chains][iterations][nll] and values [chains][iterations][nval] (predictions or replicated observations;
+    the two may be one buffer), computed where they are (rh_loo_expect_device).  Result k pairs log-likelihood column ll_cols[k]
+    with value column val_cols[k]; y [len(ll_cols)]: the observations, for the LOO-PIT."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_loo_expect_device(C.c_void_p(ll_ptr), int(nll), C.c_void_p(val_ptr), int(nval), int(device), int(chains),
+                                                       int(iterations), int(first), count, int(thin), *a)
+    return _loo_expect_result(call, nll, nval, ll_cols, val_cols, y)
+
+
 def histogram_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
                      thin: int = 1, cols: Optional[Sequence[int]] = None, bins: int = 20, range=None) -> Histogram:
     """Histograms of the pooled kept iterations first + j * thin of a device buffer [chains][iterations][nvars] (a sampler's draws, a
@@ -855,6 +908,22 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_loo(self._h, predictor._h, int(first), count, int(thin), *a)
         return _loo_result(call, predictor.nreq, cols, self.model._h)
+
+    def loo_expect(self, ll_predictor: Predictor, predictor: Predictor, ll_cols: Optional[Sequence[int]] = None,
+                   val_cols: Optional[Sequence[int]] = None, y: Optional[Sequence[float]] = None, generator: Optional[Generator] = None,
+                   seed: int = 0, first: int = 0, count: Optional[int] = None, thin: int = 1) -> LooExpect:
+        """Is the model calibrated: the leave-one-out predictive mean and variance of every observation, its LOO-PIT against y and
+        the PSIS effective sample size (the `loo` package's E_loo and loo_pit) over the kept iterations first + j * thin of every
+        chain.  ll_predictor's requirements are the pointwise log-likelihoods; the values are `predictor`'s requirements or, with a
+        generator, the samples it draws from them (with `seed`, the bits of Sampler.generate(predictor, generator, seed)).  Both
+        matrices are made and reduced on the device (rh_sampler_loo_expect) and never leave it.  Result k pairs log-likelihood column
+        ll_cols[k] with value column val_cols[k]; None: column i with column i up to the narrower width.  count = None: everything
+        completed so far.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_loo_expect(self._h, ll_predictor._h, predictor._h, generator._h if generator is not None else None,
+                                                            int(seed), int(first), count, int(thin), *a)
+        return _loo_expect_result(call, ll_predictor.nreq, generator.nout if generator is not None else predictor.nreq, ll_cols, val_cols, y,
+                                  self.model._h)
 
     def mass_dense(self) -> np.ndarray:
         """DenseMassMatrix.elements of every chain: [chains][nVars][nVars] (DenseMassMatrixTuner only)."""
