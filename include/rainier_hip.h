@@ -637,6 +637,67 @@ int rh_sampler_loo_expect(rh_sampler *s, rh_predict *p_ll, rh_predict *p_val, rh
  * before a launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_loo_expect_lower_only(const char *arch, void **code_out, size_t *code_size);
 
+/* ---- posterior predictive checks over device-resident replicated draws -------------------------------------------------------------
+ * Does the fitted model reproduce the features of the data that were observed -- its spread, its extremes, its share of zeros, group
+ * by group (Gelman, Meng and Stern 1996; bayesplot's ppc_stat and ppc_stat_grouped) -- computed where the replicated observations are
+ * (csrc/device/rh_ppc.hip.h).  Input: rep [chains][iterations][nin], a row being one replicated data set (rh_sampler_generate's
+ * buffer); the kept iterations first + j * thin of every chain, kept = ceil(count / thin), S = chains * kept draws, flat row
+ * r = c * kept + j (rh_sampler_predict's window).  The one call that reduces along a row, over the observations.
+ * A check is a table.  cols [K]: columns of the row, duplicates allowed; NULL: all nin in order (K 0 or nin).  seg_off [nseg + 1] cuts
+ * that list into nseg non-empty runs: seg_off[0] = 0, strictly ascending, seg_off[nseg] = K; NULL: one segment (nseg 0 or 1).  Segment g
+ * of a draw is the values row[cols[seg_off[g] .. seg_off[g+1])], n_g of them.  stats [nstat], nstat >= 1, are evaluated on every
+ * segment: nout = nseg * nstat outputs per draw, T[r][g * nstat + k] -- the layout [chains][kept][nout] every other device call reads.
+ *   RH_PPC_MEAN         sum v / n
+ *   RH_PPC_SD           sqrt(sum (v - mean)^2 / (n - 1)), in two passes; n = 1: NaN (the formula's 0 / 0)
+ *   RH_PPC_MIN, _MAX    in the summaries' key order (Double.compare's): -0.0 before +0.0
+ *   RH_PPC_QUANTILE(p)  the order statistic sorted[min(n - 1, (int64)floor((double)n * p))], 0 <= p <= 1: precis' rule, the index
+ *                       computed on the host in double per (segment, statistic)
+ *   RH_PPC_FRAC_LE(c)   #{v <= c} / n, c finite: the share of zeros of count data, exceedance shares
+ * arg is p or c, and 0 for the kinds that take none; reserved is 0.
+ * Rules.  A segment that holds a NaN gives NaN in every statistic of that draw and segment, and nothing else is touched: no result
+ * depends on where a NaN sorts.  Infinities follow IEEE arithmetic (a segment with +inf: mean +inf, sd NaN).  Every NaN returned is the
+ * positive quiet NaN.  Where all keys of a segment are equal the mean is that value and, for n >= 2, the sd is 0, as rh_loo_device
+ * treats a constant column: sum c / n does not always round back to c.  Sums: with w(n) = clamp(2^ceil(log2 n) / 16, 1, 256), partial
+ * t of w(n_g) adds the segment's values i = t, t + w, .. in ascending i from +0.0, then the partials are added as a fixed binary tree
+ * (p[t] += p[t + s], s = w/2, w/4, .. 1): the order depends on n_g alone -- not on K, the other segments, the tiling or the call.  No
+ * floating-point atomics.
+ * The observed statistics.  y [nin] (indexed by input column; may be NULL): t_obs [nout] is made by the same device routine on y as a
+ * buffer of one row, so both sides of every comparison went through identical arithmetic.  For each output three counts over the S
+ * draws, plain double comparisons: n_bad = #{T is NaN}, n_gt = #{T > t_obs}, n_eq = #{T == t_obs}; a NaN t_obs gives n_gt = n_eq = 0.
+ * The Bayesian p-value is the caller's: (n_gt + n_eq) / (S - n_bad), or with half of n_eq.  With y == NULL, t_obs and the three counts
+ * are not written and may be NULL.
+ * Caps, refused from the shape alone before any launch with RH_E_UNSUPPORTED: K above 4096 (one row is staged in the workgroup's LDS;
+ * there is no tiled-row path), nstat above 16, nout above 4096. */
+enum rh_ppc_kind { RH_PPC_MEAN = 0, RH_PPC_SD = 1, RH_PPC_MIN = 2, RH_PPC_MAX = 3, RH_PPC_QUANTILE = 4, RH_PPC_FRAC_LE = 5 };
+typedef struct rh_ppc_stat { int32_t kind; int32_t reserved; double arg; } rh_ppc_stat;
+typedef struct rh_ppc rh_ppc;
+/* Validates without a device and touches none: a known kind, arg in its domain, reserved 0, every cols entry in 0 .. nin-1, the
+ * seg_off rules; otherwise RH_E_INVALID with a message that names the offending entry (the caps: RH_E_UNSUPPORTED).  device: where
+ * the check will run (-1: the device of its first call). */
+int rh_ppc_create(const rh_ppc_stat *stats, int32_t nstat, const int32_t *cols, int32_t K, const int32_t *seg_off, int32_t nseg, int32_t nin,
+                  int32_t device, rh_ppc **out);
+void rh_ppc_destroy(rh_ppc *h);
+/* the outputs per draw, nseg * nstat */
+int rh_ppc_nout(const rh_ppc *h);
+/* over any device buffer dev_rep [chains][iterations][nin] on `device` (-1: the handle's), e.g. a generator's *dev_out: on the null
+ * stream, synchronising the device before and after.  nin must be the handle's; a buffer on another device is refused.  t_obs [nout]
+ * (double), n_gt, n_eq, n_bad [nout] (int64): caller-allocated on the host, required with y.  host_out (may be NULL): caller-allocated
+ * [chains][kept][nout]; *dev_out (may be NULL): the handle's own buffer of that shape, valid until the handle's next call.  A broken
+ * window, another nin, a NULL: RH_E_INVALID.  No device: RH_E_DEVICE (no CPU fallback). */
+int rh_ppc_device(rh_ppc *h, const void *dev_rep, int32_t device, int32_t chains, int32_t iterations, int32_t nin, int32_t first, int32_t count,
+                  int32_t thin, const double *y, double *t_obs, int64_t *n_gt, int64_t *n_eq, int64_t *n_bad, double *host_out, void **dev_out);
+/* rh_sampler_generate's path -- p over the window, g over p's output with the same seed rule, so the same y_rep bits -- then the check
+ * over the generator's buffer [chains][kept][g's nout], all on the sampler's stream with one synchronisation; nothing is copied to
+ * the host but what is asked for.  g's nout must be h's nin (and p's nreq g's nin) and all four objects on one device, else
+ * RH_E_INVALID.  Not part of rh_timing; the chains are not altered.  The generator's RH_GEN_F_* flags are not reported by this call:
+ * a sample outside its family's domain and a capped rejection loop are both NaN samples, so they make their segment's statistics NaN
+ * and are counted in n_bad; a caller who wants to tell the two apart runs rh_sampler_generate with the same seed. */
+int rh_sampler_ppc(rh_sampler *s, rh_predict *p, rh_generate *g, rh_ppc *h, int64_t seed, int64_t chain0, int32_t first, int32_t count, int32_t thin,
+                   const double *y, double *t_obs, int64_t *n_gt, int64_t *n_eq, int64_t *n_bad, double *host_out, void **dev_out);
+/* No device needed: the predictive check kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_ppc_lower_only(const char *arch, void **code_out, size_t *code_size);
+
 int rh_abi_version(void);
 /* number of visible HIP devices, or a negative rh_status */
 int rh_device_count(void);

@@ -45,11 +45,14 @@ EXPORTS = [
     # pointwise WAIC and PSIS-LOO over device-resident log-likelihood draws (Vehtari, Gelman, Gabry 2017)
     "rh_loo_device", "rh_sampler_loo", "rh_loo_lower_only",
     "rh_loo_expect_device", "rh_sampler_loo_expect", "rh_loo_expect_lower_only",
+    # posterior predictive checks over device-resident replicated draws (Gelman, Meng, Stern 1996)
+    "rh_ppc_create", "rh_ppc_destroy", "rh_ppc_nout", "rh_ppc_device", "rh_sampler_ppc", "rh_ppc_lower_only",
 ]
 # ... and the two whose names hold a digit, which that test's pattern of a declaration does not read (tests/test_histogram_device_cpu.py checks them)
 EXPORTS_2D = ["rh_sampler_histogram2d", "rh_histogram2d_device"]
 GEN_REAL, GEN_NORMAL, GEN_CAUCHY, GEN_LAPLACE, GEN_UNIFORM, GEN_LOGNORMAL, GEN_GAMMA, GEN_BETA, GEN_BERNOULLI, GEN_GEOMETRIC, GEN_POISSON = range(11)
 GEN_F_DOMAIN, GEN_F_CAP = 1, 2
+PPC_MEAN, PPC_SD, PPC_MIN, PPC_MAX, PPC_QUANTILE, PPC_FRAC_LE = range(6)
 
 
 class CompileOpts(C.Structure):
@@ -64,6 +67,10 @@ class GenArg(C.Structure):      # rh_gen_arg: col >= 0: column of the input buff
 
 class GenOp(C.Structure):       # rh_gen_op
     _fields_ = [("family", C.c_int32), ("reserved", C.c_int32), ("a", GenArg), ("b", GenArg)]
+
+
+class PpcStat(C.Structure):     # rh_ppc_stat: arg is QUANTILE's probability or FRAC_LE's threshold, 0 for the other kinds
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("arg", C.c_double)]
 
 
 class Config(C.Structure):
@@ -175,6 +182,12 @@ def lib():
     L.rh_loo_expect_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, ip, ip, i32, dp, dp, dp, dp, dp, dp, dp, ip]
     L.rh_sampler_loo_expect.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, i32, ip, ip, i32, dp, dp, dp, dp, dp, dp, dp, ip]
     L.rh_loo_expect_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_ppc_create.argtypes = [C.POINTER(PpcStat), i32, ip, i32, ip, i32, i32, i32, C.POINTER(vp)]
+    L.rh_ppc_destroy.restype = None; L.rh_ppc_destroy.argtypes = [vp]
+    L.rh_ppc_nout.argtypes = [vp]
+    L.rh_ppc_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, dp, dp, lp, lp, lp, dp, C.POINTER(vp)]
+    L.rh_sampler_ppc.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, i32, i32, i32, dp, dp, lp, lp, lp, dp, C.POINTER(vp)]
+    L.rh_ppc_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_comm_unique_id.argtypes = [C.c_char_p]
     L.rh_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.rh_comm_destroy.argtypes = [vp]
@@ -396,6 +409,18 @@ def loo_expect_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_loo_expect_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def ppc_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_ppc.hip.h behind rh_summary.hip.h (posterior predictive checks on the device) -> code object for `arch`, without a
+    device: compiled through the kernel cache and judged as before a launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_ppc_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -15,6 +15,7 @@
 #define RH_RANK_HOST 1
 #define RH_LOO_HOST 1
 #define RH_LOO_EXPECT_HOST 1
+#define RH_PPC_HOST 1
 #include "device/rh_trace.hip.h"
 #include "device/rh_summary.hip.h"
 #include "device/rh_cov.hip.h"
@@ -22,6 +23,7 @@
 #include "device/rh_rank.hip.h"
 #include "device/rh_loo.hip.h"
 #include "device/rh_loo_expect.hip.h"
+#include "device/rh_ppc.hip.h"
 // rh_generate.hip.h's routine needs the prelude's rng around it: the CPU test's driver defines RH_GENERATE_HOST with one in place
 #ifndef RH_GENERATE_HOST
 #define RG_CONSTANTS_ONLY 1
@@ -215,6 +217,53 @@ inline LooExpect loo_expect_plan(long long chains, long long count, long long th
   P.over_cap = P.per_pair > cap;
   P.over_lds = Q.over_lds;
   P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, K));
+  return P;
+}
+// ---- posterior predictive checks (device/rh_ppc.hip.h) ----
+struct Ppc {
+  long long kept, S;             // kept iterations per chain; flat rows (draws)
+  int K, nseg, nstat, nout;      // selected columns; segments; statistics; nseg * nstat
+  int nmax;                      // the longest segment
+  int flags;                     // PP_F_*: what the table needs
+  int team, team_log2, conc;     // lanes of an item's team, pp_width(nmax); items at once, PP_BLOCK / team
+  int stride, rows;              // doubles between two staged rows; rows of a tile (rows * stride <= PP_STAGE, at most PP_BLOCK)
+  long long tiles;               // workgroups of the stat launch
+  int sortp, sort_stride;        // slots of the longest segment's network (0: no quantile); slots between two items' scratches
+  long long lds_bytes;           // the stat launch's dynamic LDS
+  long long count_rows, count_blocks, count_lds;   // rows per workgroup, workgroups and dynamic LDS of the count launch
+  bool over_k, over_nstat, over_nout;              // beyond the caps: refused from the shape alone
+};
+// the order statistic of a QUANTILE(p) on a segment of n values: precis' rule, as summary_plan computes idx
+inline int ppc_qidx(int n, double p) { return (int)std::min<long long>(n - 1, (long long)std::floor((double)n * p)); }
+// seg_off [nseg + 1]: the runs of the K selected columns; kinds [nstat]
+inline Ppc ppc_plan(long long chains, long long count, long long thin, int K, const int *seg_off, int nseg, const int *kinds, int nstat) {
+  Ppc P = {};
+  P.kept = (count + thin - 1) / thin;
+  P.S = chains * P.kept;
+  P.K = K; P.nseg = nseg; P.nstat = nstat;
+  P.over_k = K > PP_MAX_K;
+  P.over_nstat = nstat > PP_MAX_STATS;
+  P.over_nout = (long long)nseg * nstat > PP_MAX_OUT;
+  if (P.over_k || P.over_nstat || P.over_nout) return P;
+  P.nout = nseg * nstat;
+  for (int g = 0; g < nseg; g++) P.nmax = std::max(P.nmax, seg_off[g + 1] - seg_off[g]);
+  for (int k = 0; k < nstat; k++)
+    P.flags |= kinds[k] == PP_MEAN ? PP_F_MEAN : kinds[k] == PP_SD ? PP_F_MEAN | PP_F_SD : kinds[k] == PP_QUANTILE ? PP_F_SORT : 0;
+  P.team = pp_width(P.nmax);
+  while ((1 << P.team_log2) < P.team) P.team_log2++;
+  P.conc = PP_BLOCK / P.team;
+  P.stride = pp_stride(K);
+  P.rows = std::max(1, std::min(PP_BLOCK, PP_STAGE / P.stride));
+  for (int r = P.rows; r >= 1 && (long long)P.rows * nseg > P.conc; r--)   // whole passes where a smaller tile has them
+    if ((long long)r * nseg % P.conc == 0) { P.rows = r; break; }
+  P.tiles = (P.S + P.rows - 1) / P.rows;
+  P.sortp = (P.flags & PP_F_SORT) ? pp_pow2(P.nmax) : 0;
+  P.sort_stride = pp_sort_stride(P.conc, P.sortp);
+  const long long scratch = std::max<long long>(2 * PP_BLOCK + 3 * P.conc, (long long)P.conc * P.sort_stride);
+  P.lds_bytes = 8 * ((long long)P.rows * P.stride + scratch);
+  P.count_rows = std::max<long long>(1, PP_COUNT_ELEMS / P.nout);
+  P.count_blocks = (P.S + P.count_rows - 1) / P.count_rows;
+  P.count_lds = 3ll * P.nout * 4;
   return P;
 }
 // ---- predict (device/rh_predict.hip.h) ----

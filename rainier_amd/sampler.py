@@ -736,6 +736,123 @@ def loo_expect_device(ll_ptr: int, val_ptr: int, chains: int, iterations: int, n
     return _loo_expect_result(call, nll, nval, ll_cols, val_cols, y)
 
 
+class ppc:
+    """Statistic constructors of a Check's table (rh_ppc_stat): what a posterior predictive check evaluates on every segment of every
+    replicated data set."""
+
+    @staticmethod
+    def _stat(kind, arg=0.0) -> "_capi.PpcStat": return _capi.PpcStat(kind, 0, float(arg))
+    @staticmethod
+    def mean(): return ppc._stat(_capi.PPC_MEAN)
+    @staticmethod
+    def sd(): return ppc._stat(_capi.PPC_SD)                  # divisor n - 1
+    @staticmethod
+    def min(): return ppc._stat(_capi.PPC_MIN)
+    @staticmethod
+    def max(): return ppc._stat(_capi.PPC_MAX)
+    @staticmethod
+    def quantile(p): return ppc._stat(_capi.PPC_QUANTILE, p)  # the order statistic sorted[min(n - 1, floor(n p))]: precis' rule
+    @staticmethod
+    def frac_le(c): return ppc._stat(_capi.PPC_FRAC_LE, c)    # #{v <= c} / n: frac_le(0) is the share of zeros of count data
+
+
+class Check:
+    """rh_ppc: a table of ppc.* statistics over segments of the `nin` columns of a replicated data set (Sampler.ppc, ppc_device).
+    cols: the columns selected, duplicates allowed (None: all in order); segments: a list of column lists, each a group of
+    observations the statistics are evaluated on (None: one segment, `cols` or everything); give one or the other.  nout = number
+    of segments x number of statistics."""
+
+    def __init__(self, stats, nin: int, cols: Optional[Sequence[int]] = None, segments: Optional[Sequence[Sequence[int]]] = None, device: int = -1):
+        self._h = C.c_void_p()
+        stats = list(stats)
+        if segments is not None:
+            if cols is not None:
+                raise ValueError("Check: give cols or segments, not both")
+            segments = [[int(c) for c in seg] for seg in segments]
+            cols = [c for seg in segments for c in seg]
+            off = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(seg) for seg in segments])]), dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        cc = None if cols is None else np.ascontiguousarray([int(c) for c in cols] or [0], dtype=np.int32)
+        arr = (_capi.PpcStat * max(1, len(stats)))(*stats)
+        _capi.check(_capi.lib().rh_ppc_create(arr, len(stats), None if cc is None else ip(cc), 0 if cols is None else len(cols),
+                                              None if segments is None else ip(off), 0 if segments is None else len(segments), int(nin), int(device),
+                                              C.byref(self._h)))
+        self.nin, self.nstat = int(nin), len(stats)
+        self.nout = _capi.lib().rh_ppc_nout(self._h)
+        self.nseg = self.nout // self.nstat
+
+    def close(self):
+        if self._h:
+            _capi.lib().rh_ppc_destroy(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+
+
+class Ppc(NamedTuple):
+    """A posterior predictive check: per (segment, statistic) the statistic of the observations t_obs and, over the S draws, how many
+    replicated statistics are above it (n_gt), equal to it (n_eq) and NaN (n_bad) -- all None without y; t_rep [chains][kept][nout]
+    (output g * nstat + k) on the host or None; dev_ptr: the check's own device buffer of that shape, valid until its next call."""
+    t_obs: Optional[np.ndarray]
+    n_gt: Optional[np.ndarray]
+    n_eq: Optional[np.ndarray]
+    n_bad: Optional[np.ndarray]
+    t_rep: Optional[np.ndarray]
+    dev_ptr: int
+    S: int
+
+    def _p(self, weight_eq):
+        if self.t_obs is None:
+            return np.array(np.nan)
+        with np.errstate(all="ignore"):
+            den = (self.S - self.n_bad).astype(np.float64)
+            return np.where(den > 0, (self.n_gt + weight_eq * self.n_eq) / den, np.nan)
+
+    @property
+    def p_ge(self) -> np.ndarray:
+        """the Bayesian p-value P(T(y_rep) >= T(y)) over the draws whose statistic is a number; NaN where there is none or no y"""
+        return self._p(1.0)
+
+    @property
+    def p_gt(self) -> np.ndarray:
+        return self._p(0.0)
+
+    @property
+    def p_mid(self) -> np.ndarray:
+        """(n_gt + n_eq / 2) / (S - n_bad): the mid p-value, for statistics with ties (counts, shares)"""
+        return self._p(0.5)
+
+
+def _ppc_result(call, check, chains, kept, y, to_host, model=None):
+    """shared by Sampler.ppc and ppc_device: call(y, t_obs, n_gt, n_eq, n_bad, host_out, byref(dev_out)) -> rc"""
+    yy = None if y is None else np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if yy is not None and len(yy) != check.nin:
+        raise ValueError("ppc: y has %d entries, the check reads %d columns" % (len(yy), check.nin))
+    t_obs = np.zeros(check.nout)
+    n_gt, n_eq, n_bad = (np.zeros(check.nout, dtype=np.int64) for _ in range(3))
+    out = np.zeros((chains, kept, check.nout)) if to_host else None
+    ptr = C.c_void_p()
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    _capi.check(call(None if yy is None else _capi.dptr(yy), _capi.dptr(t_obs), lp(n_gt), lp(n_eq), lp(n_bad), _capi.dptr(out) if to_host else None,
+                     C.byref(ptr)), model)
+    shape = (check.nseg, check.nstat)
+    if yy is None:
+        return Ppc(None, None, None, None, out, ptr.value, chains * kept)
+    return Ppc(t_obs.reshape(shape), n_gt.reshape(shape), n_eq.reshape(shape), n_bad.reshape(shape), out, ptr.value, chains * kept)
+
+
+def ppc_device(check: Check, ptr: int, chains: int, iterations: int, nin: int, y: Optional[Sequence[float]] = None, first: int = 0,
+               count: Optional[int] = None, thin: int = 1, device: int = 0, to_host: bool = True) -> Ppc:
+    """Does the model reproduce the data: the check's statistics of every replicated data set of a device buffer
+    [chains][iterations][nin] (a generator's to_host = False result) over the kept iterations first + j * thin, computed where they
+    are (rh_ppc_device), and with y [nin] -- the observations -- the same statistics of y and the counts of a Bayesian p-value."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_ppc_device(check._h, C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nin), int(first), count,
+                                                int(thin), *a)
+    return _ppc_result(call, check, int(chains), _kept(count, thin), y, to_host)
+
+
 def histogram_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
                      thin: int = 1, cols: Optional[Sequence[int]] = None, bins: int = 20, range=None) -> Histogram:
     """Histograms of the pooled kept iterations first + j * thin of a device buffer [chains][iterations][nvars] (a sampler's draws, a
@@ -924,6 +1041,18 @@ class Sampler:
                                                             int(seed), int(first), count, int(thin), *a)
         return _loo_expect_result(call, ll_predictor.nreq, generator.nout if generator is not None else predictor.nreq, ll_cols, val_cols, y,
                                   self.model._h)
+
+    def ppc(self, predictor: Predictor, generator: Generator, check: Check, seed: int, y: Optional[Sequence[float]] = None, first: int = 0,
+            count: Optional[int] = None, thin: int = 1, to_host: bool = True) -> Ppc:
+        """Does the fitted model reproduce the features of the data: a posterior predictive check over the kept iterations
+        first + j * thin of every chain.  The replicated observations are Sampler.generate(predictor, generator, seed)'s, bit for bit;
+        they are made and reduced on the device (rh_sampler_ppc) and never leave it.  y [generator.nout]: the observations, for
+        t_obs and the p-values' counts; count = None: everything completed so far.  The chains are not altered.  The generator's
+        flags are not reported here (generator.flags keeps its last generate call's): a sample outside its domain or from a capped
+        loop is NaN, makes its segment's statistics NaN and is counted in n_bad."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_ppc(self._h, predictor._h, generator._h, check._h, int(seed), 0, int(first), count, int(thin), *a)
+        return _ppc_result(call, check, self.chains, _kept(count, thin), y, to_host, self.model._h)
 
     def mass_dense(self) -> np.ndarray:
         """DenseMassMatrix.elements of every chain: [chains][nVars][nVars] (DenseMassMatrixTuner only)."""
