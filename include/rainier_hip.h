@@ -44,7 +44,8 @@ extern "C" {
                                  rh_sampler_histogram, rh_histogram_device, rh_sampler_histogram2d, rh_histogram2d_device, rh_histogram_lower_only,
                                  rh_sampler_rank_diagnostics, rh_rank_diagnostics_device, rh_rank_lower_only,
                                  rh_loo_device, rh_sampler_loo, rh_loo_lower_only,
-                                 rh_loo_expect_device, rh_sampler_loo_expect, rh_loo_expect_lower_only) */
+                                 rh_loo_expect_device, rh_sampler_loo_expect, rh_loo_expect_lower_only,
+                                 rh_loo_quantile_device, rh_sampler_loo_quantile, rh_loo_quantile_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -636,6 +637,64 @@ int rh_sampler_loo_expect(rh_sampler *s, rh_predict *p_ll, rh_predict *p_val, rh
 /* No device needed: the leave-one-out expectation kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as
  * before a launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_loo_expect_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- leave-one-out predictive quantiles and CRPS over device-resident draws ----------------------------------------------------------
+ * What the leave-one-out predictive distribution of each observation looks like beyond its first two moments: its quantiles (the `loo`
+ * package's E_loo(type = "quantile"), the input of ppc_loo_intervals), its continuous ranked probability score against y and its spread
+ * E|X - X'| -- functionals of the weighted empirical distribution function of a value column, computed where the draws are
+ * (csrc/device/rh_loo_quantile.hip.h).
+ * Input: as rh_loo_expect_device's: ll [chains][iterations][nll] and val [chains][iterations][nval] on one device over its window and
+ * thinning, S = chains * kept >= 2; result k pairs ll_cols[k] with val_cols[k].  probs [nprobs], 1 <= nprobs <= 16, each in [0, 1].
+ * Plain mode: dev_ll == NULL (ll_cols is then not read): every weight is 1, no log-likelihood is sorted or fitted, and pareto_k and
+ * tail_n are not written and may be NULL.  Per pair:
+ *   a. Weights.  W_s is rh_loo_expect_device's (a) and (b), bit for bit: the same tail cut, the same fit, the same mean over a group of
+ *      equal keys, exp(a[0] - l_s) outside the tail.  pareto_k and tail_n are rh_loo_device's.
+ *   b. Order.  The S pairs (key of v_s, bits of W_s) -- the key is rh_summary's: Double.compare's order, -0.0 before +0.0 -- are sorted
+ *      ascending, lexicographically: x_(1) <= .. <= x_(S) with W_(j) beside them.  W >= 0, so the bits' order is the numeric one, and the
+ *      sorted sequence is a function of the multiset alone: no result depends on the draws' order.
+ *   c. Cumulative weight.  C_j = W_(1) + .. + W_(j), added in an order fixed by S alone (a running sum over a contiguous segment
+ *      of the sorted pairs on top of the sum of the segments before it; csrc/device/rh_loo_quantile.hip.h states the segments, which
+ *      are not part of this contract).  What is promised: C is non-decreasing in j as computed, C_S is the last of them, and the same
+ *      S and multiset give the same bits.
+ *   d. Quantile at p: t = p C_S (one multiplication), j the smallest index with C_j >= t (a binary search along C).  j = 1: x_(1).
+ *      Otherwise x_(j-1) + (x_(j) - x_(j-1)) ((t - C_(j-1)) / (C_j - C_(j-1))), and x_(j) itself where t == C_j (the fraction is then 1:
+ *      the knot is returned with its own bits).  The divisor is > 0 by the choice of j.  p = 0 gives x_(1), p = 1 the largest value of
+ *      positive weight (of a weight that still moves C: behind a draw that carries all but 2^-53 of it an addition absorbs the
+ *      rest).  quantiles [k * nprobs + i].
+ *   e. Scores.  F_j = C_j / C_S and G_j = 1 - F_j; for each gap [a, b) = [x_(j), x_(j+1)), j = 1 .. S - 1, with m = min(max(y, a), b):
+ *        crps   = sum_j ((m - a) F_j^2 + (b - m) G_j^2) + max(x_(1) - y, 0) + max(y - x_(S), 0)
+ *        spread = 2 sum_j (b - a) F_j G_j                                         (= E|X - X'|;  crps = E|X - y| - spread / 2)
+ *      G_j is evaluated as R_j / C_S, R_j = W_(j+1) + .. + W_(S) the weight above x_(j), summed from behind as C is from the front,
+ *      again in an order fixed by S alone: the subtraction 1 - F_j loses every digit where a few draws carry nearly all the weight, a quotient of sums of
+ *      non-negative terms loses none.  Every term is non-negative; the terms are added in an order fixed by S alone.  crps >= 0, smaller is better (the `loo` package reports the negative).  y = +-inf gives crps = +inf.
+ * y [ncols] or NULL; crps [ncols] (needs y) and spread [ncols] may be NULL and are then not computed for output.
+ * A NaN or an infinity in the log-likelihood window gives NaN in every double of the pair and tail_n = 0; one in the value window gives
+ * NaN in the pair's quantiles, crps and spread and leaves pareto_k and tail_n intact; a NaN y[k] gives NaN in crps[k] only.  Every NaN is
+ * the positive quiet one.  A constant value column c falls out of the formulas: every quantile is c, spread = 0, crps = |c - y|.  Other
+ * pairs are never touched.
+ * Deterministic: no floating-point atomics; a second call, a window and its copy, any chunking, any order of the pair list and any
+ * order of the draws give the same bits per pair.
+ * The workspace (per pair 32 S bytes, two buffers of keys and payloads -- the log-likelihood side sorts inside the second and leaves
+ * the draws' weights there until the first merge pass over pairs --, and 8 M for the tail's weights) is bounded by 128 MiB and walked
+ * in chunks of pairs; a single pair beyond it, and one whose M is beyond the 8064 tail values a workgroup's LDS holds, return
+ * RH_E_UNSUPPORTED from the shape alone, before any launch.  A broken window, S < 2, an index out of range, ncols < 1, nprobs outside
+ * 1 .. 16, a probability outside [0, 1] (a NaN included), a NULL list or a NULL output (pareto_k, tail_n: with dev_ll), crps without y:
+ * RH_E_INVALID; the two buffers on different devices: RH_E_INVALID.  No device: RH_E_DEVICE (no CPU fallback).  Synchronises the
+ * device before and after. */
+int rh_loo_quantile_device(const void *dev_ll, int32_t nll, const void *dev_val, int32_t nval, int32_t device, int32_t chains, int32_t iterations,
+                           int32_t first, int32_t count, int32_t thin, const int32_t *ll_cols, const int32_t *val_cols, int32_t ncols, const double *y,
+                           const double *probs, int32_t nprobs, double *quantiles, double *crps, double *spread, double *pareto_k, int32_t *tail_n);
+/* rh_sampler_loo_expect's arrangement: the window through p_ll (NULL: plain mode) and p_val (they may be one predictor); with g (may be
+ * NULL), g runs over p_val's output exactly as rh_sampler_generate runs it with chain0 = 0 -- the same seed gives the same y_rep bits --
+ * and the values are the generator's outputs.  The sorts and the scan follow on the sampler's stream: one synchronisation, nothing
+ * copied to the host but the figures.  Not part of rh_timing; the chains are not altered.  p_ll, p_val and g on different devices, or
+ * g's width not p_val's: RH_E_INVALID. */
+int rh_sampler_loo_quantile(rh_sampler *s, rh_predict *p_ll, rh_predict *p_val, rh_generate *g, int64_t seed, int32_t first, int32_t count,
+                            int32_t thin, const int32_t *ll_cols, const int32_t *val_cols, int32_t ncols, const double *y, const double *probs,
+                            int32_t nprobs, double *quantiles, double *crps, double *spread, double *pareto_k, int32_t *tail_n);
+/* No device needed: the leave-one-out quantile kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before
+ * a launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_loo_quantile_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 /* ---- posterior predictive checks over device-resident replicated draws -------------------------------------------------------------
  * Does the fitted model reproduce the features of the data that were observed -- its spread, its extremes, its share of zeros, group

@@ -45,6 +45,7 @@ EXPORTS = [
     # pointwise WAIC and PSIS-LOO over device-resident log-likelihood draws (Vehtari, Gelman, Gabry 2017)
     "rh_loo_device", "rh_sampler_loo", "rh_loo_lower_only",
     "rh_loo_expect_device", "rh_sampler_loo_expect", "rh_loo_expect_lower_only",
+    "rh_loo_quantile_device", "rh_sampler_loo_quantile", "rh_loo_quantile_lower_only",
     # posterior predictive checks over device-resident replicated draws (Gelman, Meng, Stern 1996)
     "rh_ppc_create", "rh_ppc_destroy", "rh_ppc_nout", "rh_ppc_device", "rh_sampler_ppc", "rh_ppc_lower_only",
 ]
@@ -182,6 +183,9 @@ def lib():
     L.rh_loo_expect_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, ip, ip, i32, dp, dp, dp, dp, dp, dp, dp, ip]
     L.rh_sampler_loo_expect.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, i32, ip, ip, i32, dp, dp, dp, dp, dp, dp, dp, ip]
     L.rh_loo_expect_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_loo_quantile_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, ip, ip, i32, dp, dp, i32, dp, dp, dp, dp, ip]
+    L.rh_sampler_loo_quantile.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, i32, ip, ip, i32, dp, dp, i32, dp, dp, dp, dp, ip]
+    L.rh_loo_quantile_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_ppc_create.argtypes = [C.POINTER(PpcStat), i32, ip, i32, ip, i32, i32, i32, C.POINTER(vp)]
     L.rh_ppc_destroy.restype = None; L.rh_ppc_destroy.argtypes = [vp]
     L.rh_ppc_nout.argtypes = [vp]
@@ -409,6 +413,19 @@ def loo_expect_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_loo_expect_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def loo_quantile_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_loo_quantile.hip.h behind rh_summary.hip.h, rh_loo.hip.h and rh_loo_expect.hip.h (leave-one-out predictive
+    quantiles and CRPS on the device) -> code object for `arch`, without a device: compiled through the kernel cache and judged as
+    before a launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_loo_quantile_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -15,6 +15,7 @@
 #define RH_RANK_HOST 1
 #define RH_LOO_HOST 1
 #define RH_LOO_EXPECT_HOST 1
+#define RH_LOO_QUANTILE_HOST 1
 #define RH_PPC_HOST 1
 #include "device/rh_trace.hip.h"
 #include "device/rh_summary.hip.h"
@@ -23,6 +24,7 @@
 #include "device/rh_rank.hip.h"
 #include "device/rh_loo.hip.h"
 #include "device/rh_loo_expect.hip.h"
+#include "device/rh_loo_quantile.hip.h"
 #include "device/rh_ppc.hip.h"
 // rh_generate.hip.h's routine needs the prelude's rng around it: the CPU test's driver defines RH_GENERATE_HOST with one in place
 #ifndef RH_GENERATE_HOST
@@ -217,6 +219,29 @@ inline LooExpect loo_expect_plan(long long chains, long long count, long long th
   P.over_cap = P.per_pair > cap;
   P.over_lds = Q.over_lds;
   P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, K));
+  return P;
+}
+// ---- leave-one-out predictive quantiles and CRPS (device/rh_loo_quantile.hip.h) ----
+struct LooQuantile {
+  long long kept, S, M;          // as Loo's
+  long long per_pair, pc;        // workspace bytes of one pair (two buffers of keys and payloads, 32 S -- the log-likelihood side sorts inside the second -- and the tail's weights [M]); pairs per chunk
+  bool over_cap, over_lds;       // one pair alone is beyond the cap; M is beyond the tail's LDS (LL_TAIL_MAX)
+  long long tiles, mtiles;       // tile sorts and merge workgroups per pair, of either sort: the summary's plan (LQ_TILE == RS_TILE)
+  int passes;                    // merge passes of either sort; pass k merges runs of run(k)
+  long long seg;                 // draws of one thread's segment of the scan, ceil(S / LL_BLOCK)
+  long long run(int k) const { return (long long)RS_TILE << k; }
+};
+// K: the selected pairs; cap: LQ_WS_CAP_BYTES (a parameter for the CPU tests' driver, where small shapes make several chunks)
+inline LooQuantile loo_quantile_plan(long long chains, long long count, long long thin, long long K, long long cap = LQ_WS_CAP_BYTES) {
+  LooQuantile P = {};
+  const Loo Q = loo_plan(chains, count, thin, 1, cap);
+  P.kept = Q.kept; P.S = Q.S; P.M = Q.M;
+  P.tiles = Q.tiles; P.mtiles = Q.mtiles; P.passes = Q.passes;
+  P.per_pair = LQ_PAIR_BYTES(P.S, P.M);
+  P.over_cap = P.per_pair > cap;
+  P.over_lds = Q.over_lds;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, K));
+  P.seg = (P.S + LL_BLOCK - 1) / LL_BLOCK;
   return P;
 }
 // ---- posterior predictive checks (device/rh_ppc.hip.h) ----

@@ -736,6 +736,78 @@ def loo_expect_device(ll_ptr: int, val_ptr: int, chains: int, iterations: int, n
     return _loo_expect_result(call, nll, nval, ll_cols, val_cols, y)
 
 
+class LooQuantile(NamedTuple):
+    """Leave-one-out predictive quantiles and scores per selected pair (log-likelihood column ll_cols[k], value column val_cols[k]):
+    quantiles [K][len(probs)] of the PSIS-weighted predictive distribution of the value (the `loo` package's E_loo(type =
+    "quantile")), its continuous ranked probability score crps against y (>= 0, smaller is better; None without y), its spread
+    E|X - X'|, and the Pareto shape pareto_k and tail length tail_n that Loo reports for the column.  Without a log-likelihood
+    predictor (plain mode) every draw weighs the same, ll_cols is empty and pareto_k and tail_n are None.  A NaN or an infinity among
+    the log-likelihoods makes every figure of the pair NaN; one among the values makes its quantiles, crps and spread NaN."""
+    probs: Tuple[float, ...]
+    quantiles: np.ndarray
+    crps: Optional[np.ndarray]
+    spread: np.ndarray
+    pareto_k: Optional[np.ndarray]
+    tail_n: Optional[np.ndarray]
+    ll_cols: Tuple[int, ...]
+    val_cols: Tuple[int, ...]
+
+    @property
+    def abs_err(self) -> Optional[np.ndarray]:
+        """E|X - y| = crps + spread / 2"""
+        return None if self.crps is None else self.crps + 0.5 * self.spread
+
+    @property
+    def scrps(self) -> Optional[np.ndarray]:
+        """the scaled CRPS, -E|X - y| / E|X - X'| - log(E|X - X'|) / 2 (larger is better)"""
+        if self.crps is None:
+            return None
+        with np.errstate(all="ignore"):
+            return -self.abs_err / self.spread - 0.5 * np.log(self.spread)
+
+
+def _loo_quantile_result(call, plain, nll, nval, ll_cols, val_cols, y, probs, model=None):
+    """shared by Sampler.loo_quantile and loo_quantile_device: call(ll_cols, val_cols, ncols, y, probs, nprobs, quantiles, crps, spread,
+    pareto_k, tail_n) -> rc; without lists column i is paired with column i up to the narrower width (plain mode: every value column)"""
+    both = range(max(0, int(nval) if plain else min(int(nll), int(nval))))
+    vc = np.ascontiguousarray([int(c) for c in (both if val_cols is None else val_cols)], dtype=np.int32)
+    lc = vc[:0] if plain else np.ascontiguousarray([int(c) for c in (both if ll_cols is None else ll_cols)], dtype=np.int32)
+    if not plain and len(lc) != len(vc):
+        raise ValueError("loo_quantile: ll_cols and val_cols pair up: %d against %d entries" % (len(lc), len(vc)))
+    if plain and ll_cols is not None and len(ll_cols):
+        raise ValueError("loo_quantile: ll_cols without log-likelihoods")
+    k = len(vc)
+    yy = None if y is None else np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if yy is not None and len(yy) != k:
+        raise ValueError("loo_quantile: y has %d entries for %d pairs" % (len(yy), k))
+    pp = np.ascontiguousarray([float(p) for p in probs], dtype=np.float64)
+    q = np.zeros((max(k, 1), max(len(pp), 1)))
+    crps, spread, pk = (np.zeros(max(k, 1)) for _ in range(3))
+    tn = np.zeros(max(k, 1), dtype=np.int32)
+    i32p = C.POINTER(C.c_int32)
+    ip = lambda a: (a if len(a) else np.zeros(1, dtype=np.int32)).ctypes.data_as(i32p)   # an empty list is a list (refused)
+    yp = None if yy is None else _capi.dptr(yy if k else np.zeros(1))
+    _capi.check(call(None if plain else ip(lc), ip(vc), k, yp, _capi.dptr(pp if len(pp) else np.zeros(1)), len(pp), _capi.dptr(q),
+                     _capi.dptr(crps) if yy is not None else None, _capi.dptr(spread), None if plain else _capi.dptr(pk),
+                     None if plain else tn.ctypes.data_as(i32p)), model)
+    return LooQuantile(tuple(pp.tolist()), q[:k, :len(pp)], crps[:k] if yy is not None else None, spread[:k], None if plain else pk[:k],
+                       None if plain else tn[:k], tuple(lc.tolist()), tuple(vc.tolist()))
+
+
+def loo_quantile_device(ll_ptr: Optional[int], val_ptr: int, chains: int, iterations: int, nll: int, nval: int, ll_cols: Optional[Sequence[int]],
+                        val_cols: Sequence[int], probs: Sequence[float] = (0.05, 0.5, 0.95), y: Optional[Sequence[float]] = None, device: int = 0,
+                        first: int = 0, count: Optional[int] = None, thin: int = 1) -> LooQuantile:
+    """Leave-one-out predictive quantiles, CRPS and spread over the kept iterations first + j * thin of two buffers on one device,
+    log-likelihoods [chains][iterations][nll] and values [chains][iterations][nval] (predictions or replicated observations),
+    computed where they are (rh_loo_quantile_device).  Result k pairs log-likelihood column ll_cols[k] with value column val_cols[k];
+    y [len(val_cols)]: the observations, for the CRPS.  ll_ptr = None: plain mode, every draw weighs the same."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    plain = ll_ptr is None
+    call = lambda *a: _capi.lib().rh_loo_quantile_device(None if plain else C.c_void_p(ll_ptr), int(nll), C.c_void_p(val_ptr), int(nval), int(device),
+                                                         int(chains), int(iterations), int(first), count, int(thin), *a)
+    return _loo_quantile_result(call, plain, nll, nval, ll_cols, val_cols, y, probs)
+
+
 class ppc:
     """Statistic constructors of a Check's table (rh_ppc_stat): what a posterior predictive check evaluates on every segment of every
     replicated data set."""
@@ -1041,6 +1113,24 @@ class Sampler:
                                                             int(seed), int(first), count, int(thin), *a)
         return _loo_expect_result(call, ll_predictor.nreq, generator.nout if generator is not None else predictor.nreq, ll_cols, val_cols, y,
                                   self.model._h)
+
+    def loo_quantile(self, ll_predictor: Optional[Predictor], predictor: Predictor, probs: Sequence[float] = (0.05, 0.5, 0.95),
+                     ll_cols: Optional[Sequence[int]] = None, val_cols: Optional[Sequence[int]] = None, first: int = 0, count: Optional[int] = None,
+                     thin: int = 1, y: Optional[Sequence[float]] = None, generator: Optional[Generator] = None, seed: Optional[int] = None) -> LooQuantile:
+        """What the leave-one-out predictive distribution of every observation looks like: its quantiles at `probs` (the `loo`
+        package's E_loo(type = "quantile"): the 90 % interval by default), its CRPS against y and its spread E|X - X'|, over the kept
+        iterations first + j * thin of every chain.  ll_predictor's requirements are the pointwise log-likelihoods (None: plain mode,
+        the posterior predictive distribution itself); the values are `predictor`'s requirements or, with a generator, the samples it
+        draws from them (with `seed`, the bits of Sampler.generate(predictor, generator, seed); None: 0).  Both matrices are made,
+        sorted and scanned on the device (rh_sampler_loo_quantile) and never leave it.  Result k pairs log-likelihood column
+        ll_cols[k] with value column val_cols[k]; None: column i with column i up to the narrower width.  The chains are not
+        altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        plain = ll_predictor is None
+        call = lambda *a: _capi.lib().rh_sampler_loo_quantile(self._h, None if plain else ll_predictor._h, predictor._h,
+                                                              generator._h if generator is not None else None, int(seed or 0), int(first), count, int(thin), *a)
+        return _loo_quantile_result(call, plain, 0 if plain else ll_predictor.nreq, generator.nout if generator is not None else predictor.nreq, ll_cols,
+                                    val_cols, y, probs, self.model._h)
 
     def ppc(self, predictor: Predictor, generator: Generator, check: Check, seed: int, y: Optional[Sequence[float]] = None, first: int = 0,
             count: Optional[int] = None, thin: int = 1, to_host: bool = True) -> Ppc:
