@@ -219,22 +219,35 @@ struct Lane {
   int first = 0, chains = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;         // (lane 0 runs on the model's stream)
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  std::vector<hipEvent_t> ev;
+  hipEvent_t e0 = nullptr, e1 = nullptr;   // the span of a call's first tick
+  // Two event pools, used by alternate rounds: r0 / r1 the span of the round that used the pool, ev[2 i], ev[2 i + 1] around its
+  // gradient launch i.  A pool is recorded again only after the round that used it has been resolved (resolve_round).
+  hipEvent_t r0[2] = {nullptr, nullptr}, r1[2] = {nullptr, nullptr};
+  std::vector<hipEvent_t> ev[2];
   void *d_running = nullptr, *d_list = nullptr, *d_nlive = nullptr, *d_graderr = nullptr;
-  void *d_livelog = nullptr;       // [257] live counts logged by rh_compact_kernel, one per tick of a batch (+ the call's first tick)
+  void *d_livelog = nullptr;       // [round cap + 1] live counts logged by rh_compact_kernel, one per tick of a round (+, in the last slot, the call's first tick)
   void *d_partial = nullptr, *d_partial2 = nullptr;   // (the second one: fused launches)
   int pp = 0;                      // which of the two partial-sum / record buffers the next launch writes
   int cur_live = 0;                // chains in the list the next gradient launch serves
   GatherBufs *gb = nullptr;
   // views into the sampler's arrays at chain `first`
   void *state = nullptr, *seeds = nullptr, *draws = nullptr, *stats = nullptr, *qbuf = nullptr, *active = nullptr, *rec[2] = {nullptr, nullptr};
-  // host side of a batch in flight
-  int running = 0, B = 0, remaining_hint = 32;
+  // host side of a round in flight
+  int running = 0, B = 0;
+  long long remaining = 0;         // gradient launches this call still has to do (exact in a lock-step run; lanes_plan.hpp round_launches)
   long long pos = 0;               // gradient launches since the first tick of this call
   bool live = false;               // still advancing in this call
-  std::vector<int> livelog;
-  std::vector<char> was_ticked;
+  bool pending = false, prev_rec = false;   // the previous launch's gradient has not been consumed by a tick / it left records
+  // per event pool, for resolve_round: the host copy of the round's live log and which of its launches a tick followed
+  std::vector<int> livelog[2];
+  std::vector<char> was_ticked[2];
+};
+// A finished round whose timing figures have not been read out of its events yet (resolve_round)
+struct RoundRec {
+  bool open = false;
+  int pool = 0;
+  bool live[2] = {false, false};   // the lanes that took part
+  int B[2] = {0, 0};               // ... and their launches
 };
 
 struct rh_sampler {
@@ -263,6 +276,9 @@ struct rh_sampler {
   bool lane_walk = false;          // the gradient launches are rh_grad_lane_kernel's (lanes_plan.hpp walk_is_lane; fixed at creation)
   bool lane_rows = false;          // ... the row-fed rh_grad_lane_kernel's: the lane walk fed from the interleaved copies (feed_is_rows; fixed at creation)
   std::vector<Lane> lanes;         // one, or two halves of the chains on two streams (lanes_plan.hpp)
+  int round_cap = 0;               // gradient launches per lane of a round at the most (lanes_plan.hpp round_cap; RH_ROUND_MAX)
+  int next_pool = 0;               // the event pool the next round records
+  RoundRec round;                  // the last round, until its figures have been added to kernel_ms ... launches above
   std::vector<rh_chain_stats_dev> last_stats;
   int64_t grads_at_reset = 0;
 };
@@ -1716,12 +1732,17 @@ int lane_nsplit(const rh_model *m, int total_chains) {
   return rh_plan::lane_nsplit(total_chains, lane_max_rows(m));
 }
 // the feed of a lane walk's launches: RH_LANE_FEED=cols|rows (RH_DIAG) forces it; `rows` is the column feed where the model has no
-// row-fed kernel.  The two feeds give a chain the same bits, so every shard decides for itself.
+// row-fed kernel.  The two feeds give a chain the same bits, so every shard decides for itself.  Decided where a sampler is created
+// and where a density evaluation begins, not launch by launch: a copy holds the rows that were uploaded, and should data.nrows
+// name more at that moment, the launches take the column feed.
 bool feed_is_rows(rh_model *m) {
   int forced = 0;
   if (const char *e = rh::knob("RH_LANE_FEED")) forced = std::strcmp(e, "cols") == 0 ? 1 : (std::strcmp(e, "rows") == 0 ? 2 : 0);
   if (!rh_plan::feed_is_rows(true, forced)) return false;   // (no reason to build the kernel and the copies)
-  return rh_plan::feed_is_rows(ensure_lane_rows(m) != nullptr, forced);
+  if (!rh_plan::feed_is_rows(ensure_lane_rows(m) != nullptr, forced)) return false;
+  std::vector<long long> want;
+  for (size_t t = 0; t < m->prog.targets.size(); t++) if (m->prog.targets[t].n_cols) want.push_back(m->data.nrows[t]);
+  return m->k_grad_lane_rows && rh_plan::lane_rows_cover((int)want.size(), want.data(), (int)m->dev_rows_n.size(), m->dev_rows_n.data(), m->dev_rows.data());
 }
 
 // one batched gradient launch of the tick engine: whichever row-streaming kernel the model was lowered to
@@ -1734,13 +1755,7 @@ void launch_grad(rh_model *m, GatherBufs *gb, void *d_q, void *d_list, void *d_n
   if (!stream) stream = m->stream;
   if (lane_walk) {   // rh_grad_lane_kernel: 64 C chains per group, W wavefronts per workgroup, rh_grad_kernel's arguments
     const int lgroups = (chains + rh_plan::kLaneGroup - 1) / rh_plan::kLaneGroup;
-    // (a copy holds the rows that were uploaded; should data.nrows ever name more, the launch takes the column feed: the same bits)
-    if (lane_rows) {
-      std::vector<long long> want;
-      for (size_t t = 0; t < m->prog.targets.size(); t++) if (m->prog.targets[t].n_cols) want.push_back(m->data.nrows[t]);
-      lane_rows = m->k_grad_lane_rows && rh_plan::lane_rows_cover((int)want.size(), want.data(), (int)m->dev_rows_n.size(), m->dev_rows_n.data(), m->dev_rows.data());
-    }
-    if (lane_rows) {   // the row-fed rh_grad_lane_kernel: the same, with the interleaved copies' addresses (struct rh_lane_rows) behind the model's data
+    if (lane_rows) {   // (the caller has asked feed_is_rows, which looks at the copies) the row-fed rh_grad_lane_kernel: the same, with the interleaved copies' addresses (struct rh_lane_rows) behind the model's data
       void *ra[] = {&m->data, m->dev_rows.data(), &d_q, &d_list, &d_nlive, &d_vflag, &d_partial, &d_graderr, &d_running, &chains, &nsplit, &xcd};
       launch(m->k_grad_lane_rows, (unsigned)(lgroups * nsplit), 64 * rh_plan::kLaneW, stream, ra);
       return;
@@ -2100,6 +2115,11 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
       const rh_plan::LaneCut cut = rh_plan::lanes_cut(chains, s->lane_walk ? rh_plan::kLaneGroup : m->k_grad_glm ? 16 : m->grad_k, nsplit,
                                                       s->lane_walk ? rh_plan::kLaneW : m->k_grad_glm ? m->glm_w : 1, device_cus(m->device), forced);
       s->lanes.resize((size_t)cut.lanes);
+      // The longest round (lanes_plan.hpp round_launches) sizes each lane's live log and event pools; RH_ROUND_MAX=n lowers it, so
+      // that tests cross round boundaries at tiny sizes.
+      s->round_cap = rh_plan::kRoundCapDefault;
+      if (const char *e = rh::knob("RH_ROUND_MAX")) s->round_cap = rh_plan::round_cap(std::atoi(e));
+      const size_t cap = (size_t)s->round_cap;
       const size_t iters_alloc = (size_t)cfg->iterations;   // (a chain's draws are addressed as chain * cfg.iterations * n)
       for (int li = 0; li < cut.lanes; li++) {
         Lane &L = s->lanes[(size_t)li];
@@ -2109,6 +2129,7 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
         else { HIPCHK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking)); L.own_stream = true; }
         HIPCHK(hipEventCreate(&L.e0));
         HIPCHK(hipEventCreate(&L.e1));
+        for (int p = 0; p < 2; p++) { HIPCHK(hipEventCreate(&L.r0[p])); HIPCHK(hipEventCreate(&L.r1[p])); }
         L.state = (uint64_t *)s->d_state + (size_t)f * s->state_words;
         L.seeds = (int64_t *)s->d_seeds + (size_t)2 * f;
         L.draws = (double *)s->d_draws + (size_t)f * iters_alloc * n;
@@ -2120,8 +2141,8 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
         HIPCHK(hipMalloc(&L.d_running, sizeof(int)));
         HIPCHK(hipMalloc(&L.d_list, sizeof(int) * lc));
         HIPCHK(hipMalloc(&L.d_nlive, sizeof(int)));
-        HIPCHK(hipMalloc(&L.d_livelog, sizeof(int) * 257));
-        HIPCHK(hipMemset(L.d_livelog, 0, sizeof(int) * 257));
+        HIPCHK(hipMalloc(&L.d_livelog, sizeof(int) * (cap + 1)));
+        HIPCHK(hipMemset(L.d_livelog, 0, sizeof(int) * (cap + 1)));
         { std::vector<int> ident((size_t)lc);   // (the list of a sampler that does not compact: every chain, every launch)
           for (int c = 0; c < lc; c++) ident[(size_t)c] = c;
           HIPCHK(hipMemcpy(L.d_list, ident.data(), sizeof(int) * lc, hipMemcpyHostToDevice)); }
@@ -2134,8 +2155,7 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
           HIPCHK(hipMemset(L.d_partial, 0, partial_bytes));
           L.gb = new GatherBufs(); L.gb->build(m, lc, nsplit);
         }
-        L.livelog.assign(257, 0);
-        L.was_ticked.assign(256, 0);
+        for (int p = 0; p < 2; p++) { L.livelog[p].assign(cap, 0); L.was_ticked[p].assign(cap, 0); }
       }
     }
     // The buffers above were cleared with hipMemset: fill KERNELS on the null stream that return before they have run, while the
@@ -2149,15 +2169,85 @@ extern "C" int rh_sampler_create(rh_model *m, const rh_config *cfg, const int64_
   return RH_OK;
 }
 
+namespace {
+// Tick engine: the timing figures of the last finished round, read out of its events.  advance_to_ticks leaves a round as a record
+// (s->round: which lanes ran, how many launches, which event pool) and calls this only once the NEXT round is in the streams -- the
+// device works while the host asks for a few thousand elapsed times and sorts them -- or, when nothing follows, not at all: then
+// rh_sampler_timing, the sampler's next advance or its destruction does.  Only ever called after the stream synchronisation that
+// ended the round, so every event asked about has completed; and always before the round's pool is recorded again.
+//   total_ms: the union of the live lanes' [r0, r1] spans of the round.
+//   Every launch's span; with two lanes in flight on one time base (hipEventElapsedTime from one reference event works across the
+//   streams of a device), and a launch is charged its busy share: the time it ran alone + half of the time it ran beside the other
+//   lane's.  kernel_ms then is the time during which a gradient launch was running, and never exceeds total_ms.
+void resolve_round(rh_sampler *s) {
+  RoundRec &R = s->round;
+  if (!R.open) return;
+  R.open = false;   // (whatever a query below answers, the round is not asked about twice)
+  HIPCHK(hipSetDevice(s->m->device));
+  const int p = R.pool, nl = (int)s->lanes.size();
+  int nlive = 0;
+  for (int li = 0; li < nl; li++) nlive += R.live[li] ? 1 : 0;
+  hipEvent_t ref = nullptr;
+  {
+    double t0[2], t1[2], share[2];
+    int k = 0;
+    for (int li = 0; li < nl; li++) {
+      if (!R.live[li]) continue;
+      Lane &L = s->lanes[(size_t)li];
+      float a = 0, b = 0;
+      if (!ref) ref = L.r0[p]; else HIPCHK(hipEventElapsedTime(&a, ref, L.r0[p]));
+      HIPCHK(hipEventElapsedTime(&b, L.r0[p], L.r1[p]));
+      t0[k] = a; t1[k] = (double)a + b; k++;
+    }
+    s->total_ms += k == 1 ? t1[0] - t0[0] : rh_plan::busy_shares(k, t0, t1, share);
+  }
+  std::vector<double> t0, t1, share;
+  for (int li = 0; li < nl; li++) {
+    if (!R.live[li]) continue;
+    Lane &L = s->lanes[(size_t)li];
+    for (int i = 0; i < R.B[li]; i++) {
+      float a = 0, g = 0;
+      if (nlive > 1) HIPCHK(hipEventElapsedTime(&a, ref, L.ev[p][(size_t)2 * i]));
+      HIPCHK(hipEventElapsedTime(&g, L.ev[p][(size_t)2 * i], L.ev[p][(size_t)2 * i + 1]));
+      t0.push_back(a); t1.push_back((double)a + g);
+    }
+  }
+  share.resize(t0.size());
+  if (nlive > 1) rh_plan::busy_shares((int)t0.size(), t0.data(), t1.data(), share.data());
+  else for (size_t i = 0; i < t0.size(); i++) share[i] = t1[i] - t0[i];
+  size_t at = 0;
+  for (int li = 0; li < nl; li++) {
+    if (!R.live[li]) continue;
+    Lane &L = s->lanes[(size_t)li];
+    for (int i = 0; i < R.B[li]; i++, at++) {
+      const double g = share[at];
+      s->kernel_ms += g;
+      // launch i served the chains listed by the last compaction before it (rounds are resolved in order: cur_live is carried from
+      // the call's first tick through every round)
+      const int served = L.cur_live;
+      s->chain_slots += served;
+      if ((int64_t)served * 10 >= (int64_t)L.chains * 9) { s->steady_ms += g; s->steady_launches += 1; s->steady_evals += served; }
+      if (s->compact && L.was_ticked[p][(size_t)i]) L.cur_live = L.livelog[p][(size_t)i];
+    }
+    s->launches += R.B[li];
+  }
+}
+}  // namespace
+
 extern "C" void rh_sampler_destroy(rh_sampler *s) {
   if (!s) return;
   if (s->m) hipSetDevice(s->m->device);
+  if (s->m) (void)guard(nullptr, [&] { resolve_round(s); });   // (nobody reads the figures any more: the record is closed so that no pool is left recorded and unread)
   for (void *p : {s->d_state, s->d_seeds, s->d_mass, s->d_draws, s->d_stats, s->d_running, s->d_qbuf, s->d_active, s->d_rec[0], s->d_rec[1]})
     if (p) hipFree(p);
   for (Lane &L : s->lanes) {
     for (void *p : {L.d_running, L.d_list, L.d_nlive, L.d_livelog, L.d_partial, L.d_partial2, L.d_graderr})
       if (p) hipFree(p);
-    for (hipEvent_t e : L.ev) hipEventDestroy(e);
+    for (int p = 0; p < 2; p++) {
+      for (hipEvent_t e : L.ev[p]) hipEventDestroy(e);
+      if (L.r0[p]) hipEventDestroy(L.r0[p]);
+      if (L.r1[p]) hipEventDestroy(L.r1[p]);
+    }
     if (L.e0) hipEventDestroy(L.e0);
     if (L.e1) hipEventDestroy(L.e1);
     delete L.gb;
@@ -2171,11 +2261,15 @@ extern "C" void rh_sampler_destroy(rh_sampler *s) {
 namespace {
 // tick engine: [tick, all chains] [compact] then repeat { [grad] [tick] [compact] } until no chain asks for a gradient any more.
 // rh_compact_kernel lists the chains whose tick asked for a gradient; the gradient launch and the tick behind it serve exactly those.
-// With two lanes every step below is taken for lane 0 and then for lane 1 -- a whole batch is enqueued on one lane's stream before
-// the other's, the device interleaves them -- and a lane whose chains have all arrived drops out of the rounds that follow.
+// The launches go out in ROUNDS (lanes_plan.hpp round_launches: a lock-step run's whole remainder, 32 otherwise), each ended by a
+// synchronisation and the read-back of `running`.  With two lanes a round is enqueued step-major -- launch i of lane 0, launch i of
+// lane 1, launch i + 1 of lane 0, ... -- so that both streams have work from the round's first microseconds to its last and neither
+// lane runs a stretch alone while the host is still busy with the other's launches; a lane whose chains have all arrived drops out of
+// the rounds that follow.  What a round means for the timing figures is read out of its events later (resolve_round).
 void advance_to_ticks(rh_sampler *s, int it_stop) {
   rh_model *m = s->m;
   HIPCHK(hipSetDevice(m->device));
+  resolve_round(s);   // (a round the last call left unread)
   int nsplit = s->nsplit, stop = it_stop, xcd = s->xcd_aware;
   void *no_list = nullptr;
   bool value_free = true;   // gradient-only requests (RH_VALUE_FREE=0: every launch computes the log-density too)
@@ -2221,13 +2315,10 @@ void advance_to_ticks(rh_sampler *s, int it_stop) {
   // launch that follows performs itself in its prologue.  (A chain that is out of step anyway is simply served by the next tick.)
   const int Ltraj = std::max(1, s->cfg.hmc_steps);
   const bool fuse_now = s->fuse && s->warmed && s->cfg.sampler == RH_SAMPLER_HMC && Ltraj > 1;
-  // batch size between host checks: exact for static HMC in the sampling phase, otherwise 32 ticks
-  int remaining_hint = 32;
-  if (s->cfg.sampler == RH_SAMPLER_HMC && s->warmed) {
-    const int iters = it_stop - (s->cfg.warmup + s->it_done);
-    remaining_hint = std::max(1, iters * std::max(1, s->cfg.hmc_steps));
-  }
-  // the union of the live lanes' [e0, e1] spans of this round -> total_ms
+  // launches between host checks: the count is exact for static HMC in the sampling phase (lanes_plan.hpp round_launches)
+  const bool lock_step = s->cfg.sampler == RH_SAMPLER_HMC && s->warmed;
+  const long long todo = lock_step ? (long long)std::max(0, it_stop - (s->cfg.warmup + s->it_done)) * Ltraj : 0;
+  // the union of the lanes' [e0, e1] spans of the call's first tick -> total_ms (two or three queries: not worth deferring)
   auto add_total = [&]() {
     hipEvent_t ref = nullptr;
     double t0[2], t1[2], share[2];
@@ -2242,22 +2333,47 @@ void advance_to_ticks(rh_sampler *s, int it_stop) {
     s->total_ms += k == 1 ? t1[0] - t0[0] : rh_plan::busy_shares(k, t0, t1, share);
   };
   for (Lane &L : s->lanes) {
-    L.live = true; L.pos = 0; L.remaining_hint = remaining_hint;
+    L.live = true; L.pos = 0; L.remaining = todo;
     HIPCHK(hipEventRecord(L.e0, L.stream));
-    tick(L, s->started ? 0 : 1, true, L.d_partial, false, 256);
+    tick(L, s->started ? 0 : 1, true, L.d_partial, false, s->round_cap);   // (its live count: the slot behind a round's)
     HIPCHK(hipEventRecord(L.e1, L.stream));
   }
   s->started = true;
-  std::vector<double> t0, t1, share;
+  // One launch of a round on one lane: [event] gradient [event], and -- unless the fused launch that follows does the update itself --
+  // the tick that consumes it, with its compaction
+  auto step = [&](Lane &L, int pool, int i) {
+    void *pbuf[2] = {L.d_partial, L.d_partial2};
+    std::vector<hipEvent_t> &ev = L.ev[pool];
+    while (ev.size() < (size_t)2 * (i + 1)) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); ev.push_back(e); }   // (while the device works on the launches before)
+    // the last launch of a round is always followed by a tick: it is the tick that counts the chains still running
+    const bool ticked = !(fuse_now && (int)(L.pos % Ltraj) + 1 < Ltraj && i != L.B - 1);
+    const int cur = fuse_now ? L.pp : 0;
+    HIPCHK(hipEventRecord(ev[(size_t)2 * i], L.stream));
+    if (L.pending) grad_fused(L, pbuf[cur ^ 1], pbuf[cur], L.prev_rec ? L.rec[cur ^ 1] : nullptr, L.rec[cur]);
+    else grad(L, pbuf[cur]);
+    HIPCHK(hipEventRecord(ev[(size_t)2 * i + 1], L.stream));
+    L.prev_rec = L.pending;
+    if (ticked) {
+      if (L.prev_rec) absorb(L, L.rec[cur]);
+      tick(L, 0, false, pbuf[cur], true, i);
+    }
+    L.pending = !ticked;
+    L.was_ticked[pool][(size_t)i] = ticked ? 1 : 0;
+    if (fuse_now) L.pp ^= 1;
+    L.pos++;
+  };
   for (bool first = true;; first = false) {
+    // (a copy to pageable host memory returns when it is done: the read-backs come after ALL lanes' launches have been enqueued)
     for (Lane &L : s->lanes) {
       if (!L.live) continue;
       L.running = 0;
       HIPCHK(hipMemcpyAsync(&L.running, L.d_running, sizeof(int), hipMemcpyDeviceToHost, L.stream));
-      if (first && s->compact) HIPCHK(hipMemcpyAsync(&L.cur_live, (int *)L.d_livelog + 256, sizeof(int), hipMemcpyDeviceToHost, L.stream));
+      if (first && s->compact) HIPCHK(hipMemcpyAsync(&L.cur_live, (int *)L.d_livelog + s->round_cap, sizeof(int), hipMemcpyDeviceToHost, L.stream));
+      if (!first && s->compact) HIPCHK(hipMemcpyAsync(L.livelog[s->round.pool].data(), L.d_livelog, sizeof(int) * (size_t)L.B, hipMemcpyDeviceToHost, L.stream));
     }
     for (Lane &L : s->lanes) if (L.live) HIPCHK(hipStreamSynchronize(L.stream));
-    add_total();
+    if (first) add_total();
+    else s->round.open = true;   // the round is over and its events have completed: from here on it may be resolved
     int nlive_lanes = 0;
     for (Lane &L : s->lanes) {
       if (!L.live) continue;
@@ -2265,70 +2381,31 @@ void advance_to_ticks(rh_sampler *s, int it_stop) {
       if (L.running == 0) L.live = false; else nlive_lanes++;
     }
     if (nlive_lanes == 0) break;
-    for (Lane &L : s->lanes) {
+    // The next round, step-major, into the event pool the last round did not use
+    const int pool = s->next_pool;
+    RoundRec next;
+    next.pool = pool;
+    int maxB = 0;
+    for (size_t li = 0; li < s->lanes.size(); li++) {
+      Lane &L = s->lanes[li];
       if (!L.live) continue;
-      void *pbuf[2] = {L.d_partial, L.d_partial2};
-      const int B = L.B = std::min(L.remaining_hint, 256);
-      while ((int)L.ev.size() < 2 * B) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); L.ev.push_back(e); }
-      HIPCHK(hipEventRecord(L.e0, L.stream));
-      bool pending = false, prev_rec = false;   // the previous launch's gradient has not been consumed by a tick / it left records
-      for (int i = 0; i < B; i++) {
-        // the last launch of a batch is always followed by a tick: it is the tick that counts the chains still running
-        const bool ticked = !(fuse_now && (int)(L.pos % Ltraj) + 1 < Ltraj && i != B - 1);
-        const int cur = fuse_now ? L.pp : 0;
-        HIPCHK(hipEventRecord(L.ev[2 * i], L.stream));
-        if (pending) grad_fused(L, pbuf[cur ^ 1], pbuf[cur], prev_rec ? L.rec[cur ^ 1] : nullptr, L.rec[cur]);
-        else grad(L, pbuf[cur]);
-        HIPCHK(hipEventRecord(L.ev[2 * i + 1], L.stream));
-        prev_rec = pending;
-        if (ticked) {
-          if (prev_rec) absorb(L, L.rec[cur]);
-          tick(L, 0, false, pbuf[cur], true, i);
-        }
-        pending = !ticked;
-        L.was_ticked[(size_t)i] = ticked ? 1 : 0;
-        if (fuse_now) L.pp ^= 1;
-        L.pos++;
-      }
-      HIPCHK(hipEventRecord(L.e1, L.stream));
+      L.B = rh_plan::round_launches(lock_step, lock_step ? L.remaining : rh_plan::kRoundHint, Ltraj, s->round_cap);
+      L.pending = L.prev_rec = false;
+      next.live[li] = true; next.B[li] = L.B;
+      maxB = std::max(maxB, L.B);
+      HIPCHK(hipEventRecord(L.r0[pool], L.stream));
     }
-    // (a copy to pageable host memory returns when it is done: the read-backs come after BOTH lanes' batches have been enqueued)
-    for (Lane &L : s->lanes)
-      if (L.live && s->compact) HIPCHK(hipMemcpyAsync(L.livelog.data(), L.d_livelog, sizeof(int) * (size_t)L.B, hipMemcpyDeviceToHost, L.stream));
-    for (Lane &L : s->lanes) if (L.live) HIPCHK(hipStreamSynchronize(L.stream));
-    // Every launch's span; with two lanes in flight on one time base (hipEventElapsedTime from one reference event works across
-    // the streams of a device), and a launch is charged its busy share: the time it ran alone + half of the time it ran beside the
-    // other lane's.  kernel_ms then is the time during which a gradient launch was running, and never exceeds total_ms.
-    t0.clear(); t1.clear();
-    hipEvent_t ref = nullptr;
-    for (Lane &L : s->lanes) {
-      if (!L.live) continue;
-      if (!ref && nlive_lanes > 1) ref = L.e0;
-      for (int i = 0; i < L.B; i++) {
-        float a = 0, g = 0;
-        if (ref) HIPCHK(hipEventElapsedTime(&a, ref, L.ev[2 * i]));
-        HIPCHK(hipEventElapsedTime(&g, L.ev[2 * i], L.ev[2 * i + 1]));
-        t0.push_back(a); t1.push_back((double)a + g);
+    for (int i = 0; i < maxB; i++)
+      for (Lane &L : s->lanes) {
+        if (!L.live || i >= L.B) continue;
+        step(L, pool, i);
+        if (i == L.B - 1) HIPCHK(hipEventRecord(L.r1[pool], L.stream));
       }
-    }
-    share.resize(t0.size());
-    if (nlive_lanes > 1) rh_plan::busy_shares((int)t0.size(), t0.data(), t1.data(), share.data());
-    else for (size_t i = 0; i < t0.size(); i++) share[i] = t1[i] - t0[i];
-    size_t at = 0;
-    for (Lane &L : s->lanes) {
-      if (!L.live) continue;
-      for (int i = 0; i < L.B; i++, at++) {
-        const double g = share[at];
-        s->kernel_ms += g;
-        // launch i served the chains listed by the last compaction before it
-        const int served = L.cur_live;
-        s->chain_slots += served;
-        if ((int64_t)served * 10 >= (int64_t)L.chains * 9) { s->steady_ms += g; s->steady_launches += 1; s->steady_evals += served; }
-        if (s->compact && L.was_ticked[(size_t)i]) L.cur_live = L.livelog[(size_t)i];
-      }
-      s->launches += L.B;
-      L.remaining_hint = std::max(32, L.remaining_hint - L.B);
-    }
+    // the device has this round to work on: time to read the last one's figures out of the other pool
+    resolve_round(s);
+    s->round = next;
+    s->next_pool = pool ^ 1;
+    for (Lane &L : s->lanes) if (L.live) L.remaining = std::max(0LL, L.remaining - L.B);
   }
 }
 
@@ -2527,6 +2604,7 @@ extern "C" int rh_sampler_timing(rh_sampler *s, rh_timing *out, int reset) {
   std::lock_guard<std::mutex> lk(s->m->mu);
   return guard(s->m, [&] {
     fetch_stats(s);
+    resolve_round(s);   // (the last round of the last advance: nothing followed it that could have hidden the read-out)
     int64_t grads = 0;
     for (auto &d : s->last_stats) grads += d.gradient_evaluations;
     std::memset(out, 0, sizeof(*out));

@@ -103,6 +103,24 @@ inline bool feed_is_rows(bool model_has_rows_kernel, int forced) {
   return forced == 2 || kLaneFeedRowsDefault;
 }
 
+// ---- the rounds of a run ----
+// advance_to_ticks enqueues a ROUND of gradient launches (each with its tick and compaction) on every live lane, then synchronises and
+// reads how many chains still run.  A lock-step run -- static HMC in the sampling phase: every chain asks for the same launches, and
+// `remaining`, the gradient launches the call still has to do, is exact -- takes the whole remainder in one round, up to the cap: the
+// host has nothing to decide in between, and every round boundary is a stretch in which the device waits for the host.  Everything
+// else does not know how far its chains are, and asks after kRoundHint launches (never more than kRoundMaxDynamic in a round).  A
+// lock-step count that has run out while a chain still runs (a chain out of step) is no longer exact: one trajectory of `ltraj`
+// launches at a time.
+constexpr int kRoundCapDefault = 4096, kRoundMaxDynamic = 256, kRoundHint = 32;
+// the cap of a sampler's rounds, which sizes its per-lane live log and event pools: RH_ROUND_MAX=n lowers it, to 1 at the least
+inline int round_cap(int requested) { return std::max(1, std::min(requested, kRoundCapDefault)); }
+// launches of the next round; a cap below 1 reads as 1
+inline int round_launches(bool lock_step, long long remaining, int ltraj, int cap) {
+  const long long c = std::max(1, cap);
+  if (!lock_step) return (int)std::min<long long>(c, std::min<long long>(kRoundMaxDynamic, std::max<long long>(1, remaining)));
+  return (int)std::min<long long>(c, remaining > 0 ? remaining : std::max(1, ltraj));
+}
+
 // ---- the busy share of overlapping spans ----
 // n spans [t0[i], t1[i]] on one time base (t1 < t0 is read as an empty span at t0).  share[i] = the integral over span i of
 // 1 / (spans open at that instant); the shares add up to the length of the union of the spans, which is the value returned.
