@@ -391,21 +391,59 @@ int rh_summary_device(const void *dev_draws, int32_t device, int32_t chains, int
  * (Exponential(rate) is RH_GEN_GAMMA(1.0, 1 / rate), Continuous.scala:152-158.)  .toLong is Java's d2l; every output is a double.
  * No parameter can make a loop endless: GAMMA / BETA need every shape finite and > 0 and POISSON lambda finite and >= 0, else the
  * output is NaN, the op draws nothing from the stream and the call reports RH_GEN_F_DOMAIN; every rejection loop stops after 4096
- * passes with NaN and RH_GEN_F_CAP.  The return code stays RH_OK when a flag is set: the NaNs mark the samples. */
+ * passes with NaN and RH_GEN_F_CAP.  The return code stays RH_OK when a flag is set: the NaNs mark the samples.
+ *
+ * The count families and the composites (csrc/device/rh_generate_ext.hip.h, a kernel of its own: a table that uses nothing of this
+ * paragraph launches what it always launched).  rh_gen_op.reserved is a flags word and rh_gen_arg.pad a source; zeros mean what
+ * they meant.
+ *   reserved bits 0-7, the GUARD: 0 = the op always runs; j + 1 = it runs only in the draws whose SELECTOR is j.  The selector is
+ *       the sample of the nearest earlier RH_GEN_CATEGORICAL op that ran in the same draw.  A skipped op draws nothing from the
+ *       stream, raises no flag, and its value is the carry (below).  A NaN selector matches no guard.
+ *   reserved bit 8, RH_GEN_OP_HIDDEN: the op's value is not stored.  nout is the number of VISIBLE ops; output column c is the
+ *       c-th visible op.  Any other bit: RH_E_INVALID.
+ *   pad == RH_GEN_ARG_PREV (col must be -1): the argument is the draw's CARRY, the value of op o - 1 of this draw -- a skipped op's
+ *       value being the carry before it.  Not at op 0.
+ * New families are numbered from 16.  Where the reference builds an argument out of Reals, the contract is the plain left-to-right
+ * double expression written here: it differs from the reference's evaluation by rounding only, but unlike Gamma's pow it feeds
+ * a .toLong.  pow(x, 0.5) is the IEEE square root.
+ *   RH_GEN_BINOMIAL (p, k)                                                                                Discrete.scala:194-230
+ *       k >= 100 && k * p <= 10:                          min(Poisson(p * k), (long)k)                    :205-208, 223-224
+ *       else k >= 100 && k * p >= 9 && k * (1 - p) >= 9:  min(max((long)(g * sqrt(k * p * (1 - p)) + k * p), 0), (long)k)   :209-214, 225-226
+ *       else: (int)k trials (Java's saturating d2i), each one u, counting  p + 0.0 >= u   :215-217; Multinomial.scala:26-29; Generator.scala:49-57, 129-141
+ *   RH_GEN_NEGBINOMIAL (p, n)                                                                             Discrete.scala:81-109
+ *       p < -100 / n + 1 && p > 100 / n - .25:            max((long)(g * (sqrt(n * p) / (1 - p)) + n * p / (1 - p)), 0)      :95-97, 103-104
+ *       else: the sum of (long)n draws of (long)floor(log(u) / log(1 - (1 - p))), a 64-bit sum that wraps as the JVM's      :88-94, 59-69
+ *   RH_GEN_CATEGORICAL (a = the first of m consecutive weight columns, b = the immediate m, an integer in 2 .. 255)   Generator.scala:129-141
+ *       one u; cdf_i = w_i + cdf_(i-1), cdf_(-1) = 0.0; the value is the first i (from 0) with cdf_i >= u, else m - 1
+ * Composites are tables, not families.  BetaBinomial(a, b, k) (Discrete.scala:240-244) is [BETA(a, b) hidden, BINOMIAL(PREV, k)].  A
+ * mixture of m components (Discrete.scala:270-273, Continuous.scala's Mixture: Generator.categorical(components).flatMap(_.generator),
+ * the categorical's uniform first, then only the chosen component's draws) is [CATEGORICAL hidden, component 0's ops with guard 1,
+ * ..., component m - 1's ops with guard m], every component op but the last one hidden: skipped ops pass the carry through, so the
+ * last op's column is the mixture's sample in every draw -- also where a component is itself a two-op BetaBinomial.
+ * BINOMIAL / NEGBINOMIAL need p finite in [0, 1] and k / n finite and >= 0, CATEGORICAL every weight finite and >= 0: otherwise NaN,
+ * RH_GEN_F_DOMAIN and nothing drawn.  An exact path of more than 4096 trials gives NaN and RH_GEN_F_CAP and draws nothing; the
+ * Poisson and normal draws inside keep their own caps. */
 enum rh_gen_family { RH_GEN_REAL = 0, RH_GEN_NORMAL = 1, RH_GEN_CAUCHY = 2, RH_GEN_LAPLACE = 3, RH_GEN_UNIFORM = 4, RH_GEN_LOGNORMAL = 5,
-                     RH_GEN_GAMMA = 6, RH_GEN_BETA = 7, RH_GEN_BERNOULLI = 8, RH_GEN_GEOMETRIC = 9, RH_GEN_POISSON = 10 };
+                     RH_GEN_GAMMA = 6, RH_GEN_BETA = 7, RH_GEN_BERNOULLI = 8, RH_GEN_GEOMETRIC = 9, RH_GEN_POISSON = 10,
+                     RH_GEN_BINOMIAL = 16, RH_GEN_NEGBINOMIAL = 17, RH_GEN_CATEGORICAL = 18 };
+#define RH_GEN_OP_GUARD(j) ((j) + 1)   /* rh_gen_op.reserved bits 0-7: run only where the selector is j */
+#define RH_GEN_OP_HIDDEN 0x100         /* rh_gen_op.reserved bit 8 */
+#define RH_GEN_ARG_PREV 1              /* rh_gen_arg.pad */
 #define RH_GEN_F_DOMAIN 1
 #define RH_GEN_F_CAP 2
-typedef struct rh_gen_arg { int32_t col; int32_t pad; double value; } rh_gen_arg;  /* col >= 0: column of `in`; col == -1: `value` */
+typedef struct rh_gen_arg { int32_t col; int32_t pad; double value; } rh_gen_arg;  /* col >= 0: column of `in`; col == -1: `value`, or with pad == RH_GEN_ARG_PREV the carry */
 typedef struct rh_gen_op  { int32_t family; int32_t reserved; rh_gen_arg a, b; } rh_gen_op;
 typedef struct rh_generate rh_generate;
 /* A generator as a table (what Generator.zip / traverse compose, core/Generator.scala:38-47, 145-150).  Validates without a device and
  * touches none: nops in 1 .. 4096, nin >= 0, a known family, every col in -1 .. nin-1, the second
  * argument of the one-argument families (REAL, BERNOULLI, GEOMETRIC, POISSON) unused (col -1, value 0); otherwise RH_E_INVALID with
- * a message that names the op.  device: where the generator will run (-1: the device of its first call). */
+ * a message that names the op.  Likewise refused: a guard with no earlier CATEGORICAL op or beyond its m, RH_GEN_ARG_PREV at op 0 or
+ * with col != -1, a table with no visible op, a CATEGORICAL whose a is no column, whose b is no integer immediate in 2 .. 255 or whose
+ * weights end beyond nin.  device: where the generator will run (-1: the device of its first call). */
 int rh_generate_create(const rh_gen_op *ops, int32_t nops, int32_t nin, int32_t device, rh_generate **out);
 void rh_generate_destroy(rh_generate *g);
-/* the outputs per draw (= nops: one sample per op, as Generator.traverse returns one value per generator, Generator.scala:145-150) */
+/* the outputs per draw: the visible ops (= nops without RH_GEN_OP_HIDDEN: one sample per op, as Generator.traverse returns one value
+ * per generator, Generator.scala:145-150) */
 int rh_generate_nout(const rh_generate *g);
 /* Trace.predict's sampling (Trace.scala:34-41) over any device buffer dev_in [chains][kept][nin] on `device` (-1: the handle's), e.g. a
  * predictor's *dev_out: on the null stream, synchronising the device before and after.  nin must be the handle's; a buffer on
@@ -421,6 +459,8 @@ int rh_sampler_generate(rh_sampler *s, rh_predict *p, rh_generate *g, int32_t fi
 /* No device needed: the sampling kernel's code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a launch
  * (the generators of core/Continuous.scala:54-215 and core/Discrete.scala:38-186 above); *code_out is malloc'ed, freed with rh_free. */
 int rh_generate_lower_only(const char *arch, void **code_out, size_t *code_size);
+/* the same for the kernel of the count families, guards, hidden ops and carries (csrc/device/rh_generate_ext.hip.h) */
+int rh_generate_ext_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 /* ---- posterior covariance and correlation over device-resident draws --------------------------------------------------------
  * How two parameters move together: the reference's notebooks plot pairs (rainier-notebook package.scala:79-98); this is the pooled

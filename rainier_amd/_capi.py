@@ -35,7 +35,7 @@ EXPORTS = [
     # precis / hdpi over device-resident draws (rainier-notebook package.scala:327-342, 367-418)
     "rh_sampler_summary", "rh_summary_device",
     # Trace.predict of a Distribution over device-resident draws (core/Trace.scala:34-41, core/Generator.scala:171-174)
-    "rh_generate_create", "rh_generate_destroy", "rh_generate_nout", "rh_generate_device", "rh_sampler_generate", "rh_generate_lower_only",
+    "rh_generate_create", "rh_generate_destroy", "rh_generate_nout", "rh_generate_device", "rh_sampler_generate", "rh_generate_lower_only", "rh_generate_ext_lower_only",
     # covariance / correlation over device-resident draws (rainier-notebook package.scala:79-98, MassMatrixEstimator.scala:38-47)
     "rh_sampler_covariance", "rh_covariance_device", "rh_covariance_lower_only",
     # histograms / joint count grids over device-resident draws (rainier-notebook package.scala:63-98)
@@ -52,6 +52,8 @@ EXPORTS = [
 # ... and the two whose names hold a digit, which that test's pattern of a declaration does not read (tests/test_histogram_device_cpu.py checks them)
 EXPORTS_2D = ["rh_sampler_histogram2d", "rh_histogram2d_device"]
 GEN_REAL, GEN_NORMAL, GEN_CAUCHY, GEN_LAPLACE, GEN_UNIFORM, GEN_LOGNORMAL, GEN_GAMMA, GEN_BETA, GEN_BERNOULLI, GEN_GEOMETRIC, GEN_POISSON = range(11)
+GEN_BINOMIAL, GEN_NEGBINOMIAL, GEN_CATEGORICAL = 16, 17, 18   # csrc/device/rh_generate_ext.hip.h
+GEN_OP_HIDDEN, GEN_ARG_PREV = 0x100, 1                        # rh_gen_op.reserved bit 8 (bits 0-7: the guard, selector + 1); rh_gen_arg.pad
 GEN_F_DOMAIN, GEN_F_CAP = 1, 2
 PPC_MEAN, PPC_SD, PPC_MIN, PPC_MAX, PPC_QUANTILE, PPC_FRAC_LE = range(6)
 
@@ -164,6 +166,7 @@ def lib():
     L.rh_generate_device.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, dp, C.POINTER(vp), C.POINTER(C.c_int32)]
     L.rh_sampler_generate.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, dp, C.POINTER(vp), C.POINTER(C.c_int32)]
     L.rh_generate_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_generate_ext_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     ip = C.POINTER(C.c_int32)
     L.rh_sampler_covariance.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, dp, dp, dp]
     L.rh_covariance_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, dp, dp, dp]
@@ -352,6 +355,18 @@ def generate_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_generate_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def generate_ext_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_generate_ext.hip.h (the count families, guards, hidden ops and carries of posterior-predictive sampling,
+    behind rh_generate.hip.h's text) -> code object for `arch`, without a device, as generate_lower_only."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_generate_ext_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

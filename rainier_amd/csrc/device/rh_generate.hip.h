@@ -275,7 +275,7 @@ RG_FN void rg_block(const double *in, const int nin, const rg_op *ops, const int
   RG_EACH_THREAD(tid) { RG_RAISE(fl[RG_ST(tid)], flags_out); }
 }
 
-#ifndef RH_GENERATE_HOST
+#if !defined(RH_GENERATE_HOST) && !defined(RH_GENERATE_EXT)   // (rh_generate_ext.hip.h's code object holds its own kernel only)
 // grid: rh_plan::generate_tiles(nrows) workgroups of RG_TILE threads; dynamic LDS: RG_TILE * RG_STRIDE(nops) doubles
 extern "C" __global__ void __launch_bounds__(RG_TILE)
 rh_generate_kernel(const double *__restrict__ in, const int nin, const rg_op *__restrict__ ops, const int nops, const long long nrows,

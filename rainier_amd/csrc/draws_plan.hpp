@@ -31,6 +31,7 @@
 #define RG_CONSTANTS_ONLY 1
 #endif
 #include "device/rh_generate.hip.h"
+#include "device/rh_generate_ext.hip.h"
 namespace rh_plan {
 // ---- trace diagnostics (device/rh_trace.hip.h) ----
 // parameters per chunk: the workspace [chunk][chains][RT_SL] stays under the cap; whole tiles where a tile fits
@@ -315,5 +316,28 @@ inline long long generate_tiles(long long nrows) { return (nrows + RG_TILE - 1) 
 inline int generate_slab(int nops) { return RG_SLAB_W(nops); }                       // ops per slab
 inline int generate_slabs(int nops) { return (nops + generate_slab(nops) - 1) / generate_slab(nops); }
 inline size_t generate_lds_bytes(int nops) { return sizeof(double) * (size_t)RG_TILE * (size_t)RG_STRIDE(nops); }   // the launch's dynamic LDS
+// ---- its count families and composites (device/rh_generate_ext.hip.h): slabs are cut by VISIBLE outputs ----
+inline bool generate_op_visible(const rg_op &op) { return (op.reserved & RGX_HIDDEN) == 0; }
+inline int generate_visible(const rg_op *ops, int nops) { int n = 0; for (int o = 0; o < nops; o++) n += generate_op_visible(ops[o]) ? 1 : 0; return n; }   // nout
+// does the table say anything rh_generate_kernel does not read: a family from 16, a guard, HIDDEN, PREV
+inline bool generate_uses_ext(const rg_op *ops, int nops) {
+  for (int o = 0; o < nops; o++)
+    if (ops[o].family >= RGX_BINOMIAL || ops[o].reserved != 0 || ops[o].a.pad != 0 || ops[o].b.pad != 0) return true;
+  return false;
+}
+// the ops of the slab that starts at op o0: up to and with its generate_slab(nout)-th visible op and the hidden ops that follow it
+// (a slab starts at a visible op, or at op 0).  Returns the end of the slab's ops, *w: its visible ones.
+inline int generate_ext_slab_end(const rg_op *ops, int nops, int nout, int o0, int *w) {
+  int o1 = o0;
+  *w = 0;
+  while (o1 < nops && (*w < generate_slab(nout) || !generate_op_visible(ops[o1]))) { *w += generate_op_visible(ops[o1]) ? 1 : 0; o1++; }
+  return o1;
+}
+inline int generate_ext_slabs(const rg_op *ops, int nops, int nout) {
+  int n = 0, w = 0;
+  for (int o0 = 0; o0 < nops; n++) o0 = generate_ext_slab_end(ops, nops, nout, o0, &w);
+  return n;
+}
+inline size_t generate_ext_lds_bytes(int nout) { return generate_lds_bytes(nout); }   // the stride is the visible width's
 }  // namespace rh_plan
 #endif

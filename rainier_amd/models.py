@@ -193,6 +193,18 @@ def linreg_predict(k: int = 3, x=(0.5, -1.0, 2.0)):
     return g.compile_requirements([mu, g.param(0).exp()])
 
 
+def linreg_counts_predict(k: int = 3, x=(0.5, -1.0, 2.0)):
+    """Count-model parameters at a new covariate vector x over linreg()'s parameters, the columns a zero-inflated Poisson and a
+    binomial take (gen.ZeroInflated, gen.Binomial): psi = logistic(a + b.x), 1 - psi, and a rate 20 * exp(s).  The rir alone, as
+    linreg_predict; it has 3 requirements."""
+    g = Graph(2 + k, [])
+    mu = g.param(1)
+    for j in range(k):
+        mu = mu + g.param(2 + j) * float(x[j])
+    psi = 1.0 / ((-mu).exp() + 1.0)
+    return g.compile_requirements([psi, 1.0 - psi, g.param(0).exp() * 20.0])
+
+
 def sparse_predict(nvars: int = 704):
     """A prediction that reads 4 of `nvars` parameters -- the first, the last and an adjacent pair in the middle: the staging of
     csrc/device/rh_predict.hip.h that gathers the referenced slots only.  (rir, n_requirements)"""

@@ -311,13 +311,22 @@ class gen:
     (core/Trace.scala:34-41, core/Generator.scala:171-174).  Each argument is a gen.col(i) -- column i of the per-draw parameter
     buffer, e.g. requirement i of a predictor -- or a float.  Uniform(from, to) passes the kernel scale = to - from and
     Exponential(rate) passes 1 / rate, which this front end computes only from floats: with columns the caller supplies the SCALE
-    column itself (Uniform(from, scale_column), Exponential(scale_column)), e.g. as one more requirement of the predictor."""
+    column itself (Uniform(from, scale_column), Exponential(scale_column)), e.g. as one more requirement of the predictor.
+    The composites -- BetaBinomial, Mixture, ZeroInflated -- return LISTS of ops (hidden ops, guards and gen.PREV arguments:
+    csrc/device/rh_generate_ext.hip.h), which Generator flattens; each adds ONE output column, its last op's.  A mixture's weights are
+    m consecutive columns of the caller's, like every other column: e.g. m more requirements of the predictor."""
 
     class col(NamedTuple):
         index: int
 
+    class _Prev:
+        def __repr__(self): return "gen.PREV"
+    PREV = _Prev()   # as an argument: the value of the op before this one in the same draw (RH_GEN_ARG_PREV)
+
     @staticmethod
     def _arg(x) -> "_capi.GenArg":
+        if x is gen.PREV:
+            return _capi.GenArg(-1, _capi.GEN_ARG_PREV, 0.0)
         return _capi.GenArg(int(x.index), 0, 0.0) if isinstance(x, gen.col) else _capi.GenArg(-1, 0, float(x))
 
     @staticmethod
@@ -357,15 +366,68 @@ class gen:
         """rate: a float (scale = 1 / rate); a column is taken as the SCALE 1 / rate itself"""
         return gen._op(_capi.GEN_GAMMA, 1.0, rate if isinstance(rate, gen.col) else 1.0 / float(rate))
 
+    # ---- the count families and the composites (csrc/device/rh_generate_ext.hip.h)
+    @staticmethod
+    def Binomial(p, k): return gen._op(_capi.GEN_BINOMIAL, p, k)                        # Discrete.scala:194-230
+    @staticmethod
+    def NegativeBinomial(p, n): return gen._op(_capi.GEN_NEGBINOMIAL, p, n)             # :81-109
+
+    @staticmethod
+    def Categorical(first_col, m):                                                      # Generator.scala:129-141
+        """the index (0 .. m - 1) drawn with the weights in the m consecutive columns from first_col (a gen.col or an int)"""
+        first = first_col if isinstance(first_col, gen.col) else gen.col(int(first_col))
+        return gen._op(_capi.GEN_CATEGORICAL, first, int(m))
+
+    @staticmethod
+    def _copy(op, guard=None, hidden=None) -> "_capi.GenOp":
+        out = _capi.GenOp.from_buffer_copy(bytes(op))
+        if guard is not None:
+            out.reserved = (out.reserved & ~0xff) | int(guard)
+        if hidden is not None:
+            out.reserved = (out.reserved | _capi.GEN_OP_HIDDEN) if hidden else (out.reserved & ~_capi.GEN_OP_HIDDEN)
+        return out
+
+    @staticmethod
+    def hidden(op):
+        """the op with RH_GEN_OP_HIDDEN: it runs on the draw's stream, its value is not an output column"""
+        return gen._copy(op, hidden=True)
+
+    @staticmethod
+    def BetaBinomial(a, b, k):                                                          # Discrete.scala:240-244
+        """Beta(a, b).generator.flatMap(p => Binomial(p, k).generator): two ops, one column"""
+        return [gen.hidden(gen.Beta(a, b)), gen.Binomial(gen.PREV, k)]
+
+    @staticmethod
+    def Mixture(first_col, components):                                                 # Discrete.scala:270-273, Continuous.scala's Mixture
+        """Generator.categorical(components).flatMap(_.generator): the weights are the len(components) consecutive columns from
+        first_col, in the components' order; a component is an op, a composite's list of ops, or a float (gen.Real).  One column."""
+        comps = [[gen.Real(c)] if isinstance(c, (int, float)) else (list(c) if isinstance(c, (list, tuple)) else [c]) for c in components]
+        if any(op.family == _capi.GEN_CATEGORICAL or (op.reserved & 0xff) for comp in comps for op in comp):
+            raise ValueError("gen.Mixture: a component may not be a mixture itself")
+        if any(not comp for comp in comps):
+            raise ValueError("gen.Mixture: an empty component")
+        ops = [gen.hidden(gen.Categorical(first_col, len(comps)))]
+        for j, comp in enumerate(comps):
+            ops += [gen._copy(op, guard=j + 1, hidden=True) for op in comp]
+        ops[-1] = gen._copy(ops[-1], hidden=False)   # skipped ops pass the carry on: the last op's column is the sample in every draw
+        return ops
+
+    @staticmethod
+    def ZeroInflated(first_col, component):                                             # Discrete.zeroInflated
+        """0 with the weight in column first_col (psi), `component` with the weight in the next column (1 - psi, the caller's)"""
+        return gen.Mixture(first_col, [gen.Real(0.0), component])
+
 
 class Generator:
     """rh_generate: a table of gen.* ops over `nin` per-draw parameter columns, for posterior-predictive samples of draws that stay on
     the device (Sampler.generate, generate_device).  Output o of a draw is op o's sample; every draw has a java.util.Random stream
-    of its own and runs its ops left to right on it.  flags: GEN_F_DOMAIN | GEN_F_CAP of the last call (NaN samples mark the draws)."""
+    of its own and runs its ops left to right on it.  flags: GEN_F_DOMAIN | GEN_F_CAP of the last call (NaN samples mark the draws).
+    An entry of `ops` may be a composite's list of ops (gen.BetaBinomial, gen.Mixture, gen.ZeroInflated): one level of nesting is
+    flattened.  nout counts the visible ops: one column per plain op and per composite."""
 
     def __init__(self, ops, nin: int, device: int = -1):
         self._h = C.c_void_p()
-        ops = list(ops)
+        ops = [op for entry in ops for op in (entry if isinstance(entry, (list, tuple)) else [entry])]
         arr = (_capi.GenOp * max(1, len(ops)))(*ops)
         _capi.check(_capi.lib().rh_generate_create(arr, len(ops), int(nin), int(device), C.byref(self._h)))
         self.nin = int(nin)
