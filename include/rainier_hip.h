@@ -43,6 +43,7 @@ extern "C" {
                                  rh_sampler_generate, rh_sampler_covariance, rh_covariance_device, rh_covariance_lower_only,
                                  rh_sampler_histogram, rh_histogram_device, rh_sampler_histogram2d, rh_histogram2d_device, rh_histogram_lower_only,
                                  rh_sampler_rank_diagnostics, rh_rank_diagnostics_device, rh_rank_lower_only,
+                                 rh_sampler_mcse, rh_mcse_device, rh_mcse_lower_only,
                                  rh_loo_device, rh_sampler_loo, rh_loo_lower_only,
                                  rh_loo_expect_device, rh_sampler_loo_expect, rh_loo_expect_lower_only,
                                  rh_loo_quantile_device, rh_sampler_loo_quantile, rh_loo_quantile_lower_only) */
@@ -581,6 +582,47 @@ int rh_rank_diagnostics_device(const void *dev_draws, int32_t device, int32_t ch
 /* No device needed: the rank diagnostics kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_rank_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- Monte Carlo standard errors and ESS of the reported figures over device-resident draws ------------------------------------------
+ * How many digits of a mean, an sd or a quantile survive the Monte Carlo error (Vehtari et al. 2021, section 4), computed where the
+ * draws are (csrc/device/rh_mcse.hip.h): what stands next to rh_*_summary's table as the rank diagnostics stand next to a run.
+ * Input: draws [chains][iterations][nvars], the window [first, first + count) of every chain, count >= 4, no thinning; cols / ncols as
+ * for the rank diagnostics.  probs [nprobs], 0 <= nprobs <= 16, 0 < p < 1 (NULL with nprobs 0); nlags, 0 <= nlags <= 255.
+ * Split, M, h, S, the flat index, the key order and L = min(h - 1, 255) are exactly rh_rank_diagnostics_device's.
+ * Pooled figures per column, fixed-order sums whose order depends on S alone:
+ *   m = sum y / S;  E2 = sum (y - m)^2 / S;  E4 = sum (y - m)^4 / S;  sd = sqrt(S E2 / (S - 1))
+ * Series per column, each [M][h], each through the rank diagnostics' estimator unchanged (m_q, g_q(t), W, B, V, Geyer's pairs, tau_min,
+ * truncated):  A: y;  B: |y - m|;  C: (y - m)^2;  D_k: I(key(y) <= sorted[j_k]), j_k = min(S - 1, (int64) floor((double) S probs[k])),
+ * the summaries' quantile index.
+ * Outputs, caller-allocated on the host, [K] or [K][nprobs], each may be NULL:
+ *   mean = m;  sd;  ess_mean = ESS(A);  ess_sd = ESS(B);  mcse_mean = sd / sqrt(ess_mean);
+ *   mcse_sd = sqrt((E4 - E2^2) / ESS(C) / E2 / 4)  (the delta method, the form the `posterior` package uses);
+ *   quantile[k] = sorted[j_k];  ess_quantile[k] = ESS(D_k);
+ *   mcse_quantile[k] = (sorted[i2] - sorted[i1]) / 2 with e = ess_quantile[k], a = qbeta(0.15865525393145707; e p + 1, e (1 - p) + 1),
+ *   b = qbeta(0.8413447460685429; the same shapes), i1 = max(floor(a S), 1) - 1, i2 = min(ceil(b S), S) - 1  (qbeta: the inverse
+ *   regularised incomplete beta function, on the host: csrc/qbeta.hpp);
+ *   acf [K][nlags + 1]: rho_t of series A, rho_0 = 1, rho_t = 1 - (W - g(t)) / V, NaN beyond L;
+ *   truncated [K] (int32): bit 0 A, bit 1 B, bit 2 C, bit 3 + k D_k.
+ * NaN: a NaN or an infinity in the window turns every figure of that column into NaN (truncated 0), other columns are untouched; a
+ * series without W > 0 gives a NaN ESS, and every figure derived from it (the acf with series A) is NaN.
+ * Deterministic: no floating-point atomics; a second call, a window and its copy, a duplicated column and any chunking of the columns
+ * give the same bits.
+ * The workspace (per column 24 S bytes and 8 (3 + nprobs) M (L + 2): no derived series is ever written to memory) is bounded by
+ * 128 MiB and walked in chunks of columns; a single column beyond it returns RH_E_UNSUPPORTED from the shape alone, before any
+ * launch.  A broken window, count < 4, an index outside [0, nvars), ncols < 1 with a list, nprobs outside 0 .. 16, a probability
+ * outside (0, 1), nlags outside 0 .. 255: RH_E_INVALID.  No device: RH_E_DEVICE (no CPU fallback).
+ * The sampler form goes to the sampler's stream behind its pending work, is not part of rh_timing and does not alter the chains. */
+int rh_sampler_mcse(rh_sampler *s, int32_t first, int32_t count, const int32_t *cols, int32_t ncols, const double *probs, int32_t nprobs,
+                    int32_t nlags, double *mean, double *sd, double *ess_mean, double *ess_sd, double *mcse_mean, double *mcse_sd,
+                    double *quantile, double *ess_quantile, double *mcse_quantile, double *acf, int32_t *truncated);
+/* the same over any device buffer [chains][iterations][nvars] on `device` (-1: the current one); synchronises the device before and after */
+int rh_mcse_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first, int32_t count,
+                   const int32_t *cols, int32_t ncols, const double *probs, int32_t nprobs, int32_t nlags, double *mean, double *sd,
+                   double *ess_mean, double *ess_sd, double *mcse_mean, double *mcse_sd, double *quantile, double *ess_quantile,
+                   double *mcse_quantile, double *acf, int32_t *truncated);
+/* No device needed: the standard error kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_mcse_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 /* ---- pointwise WAIC and PSIS-LOO over device-resident log-likelihood draws --------------------------------------------------------
  * Which of two models predicts better (Vehtari, Gelman, Gabry 2017), computed where the draws are (csrc/device/rh_loo.hip.h).

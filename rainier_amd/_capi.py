@@ -42,6 +42,8 @@ EXPORTS = [
     "rh_sampler_histogram", "rh_histogram_device", "rh_histogram_lower_only",
     # rank-normalised split R-hat, bulk and tail ESS over device-resident draws (Vehtari et al. 2021)
     "rh_sampler_rank_diagnostics", "rh_rank_diagnostics_device", "rh_rank_lower_only",
+    # Monte Carlo standard errors and ESS of the mean, the sd and quantiles over device-resident draws (Vehtari et al. 2021, section 4)
+    "rh_sampler_mcse", "rh_mcse_device", "rh_mcse_lower_only",
     # pointwise WAIC and PSIS-LOO over device-resident log-likelihood draws (Vehtari, Gelman, Gabry 2017)
     "rh_loo_device", "rh_sampler_loo", "rh_loo_lower_only",
     "rh_loo_expect_device", "rh_sampler_loo_expect", "rh_loo_expect_lower_only",
@@ -180,6 +182,9 @@ def lib():
     L.rh_sampler_rank_diagnostics.argtypes = [vp, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_rank_diagnostics_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_rank_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_sampler_mcse.argtypes = [vp, i32, i32, ip, i32, dp, i32, i32] + [dp] * 10 + [ip]
+    L.rh_mcse_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, ip, i32, dp, i32, i32] + [dp] * 10 + [ip]
+    L.rh_mcse_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_loo_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_sampler_loo.argtypes = [vp, vp, i32, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_loo_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -403,6 +408,19 @@ def rank_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_rank_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def mcse_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_mcse.hip.h behind rh_summary.hip.h and rh_rank.hip.h (Monte Carlo standard errors and ESS of the mean, the sd
+    and quantiles on the device) -> code object for `arch`, without a device: compiled through the kernel cache and judged as before a
+    launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_mcse_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -7,12 +7,15 @@
 #include <algorithm>
 #include <cmath>
 
+#include "qbeta.hpp"
+
 // the constants are the device headers' own: their block routines compile as plain C++ in host mode
 #define RH_TRACE_HOST 1
 #define RH_SUMMARY_HOST 1
 #define RH_COV_HOST 1
 #define RH_HIST_HOST 1
 #define RH_RANK_HOST 1
+#define RH_MCSE_HOST 1
 #define RH_LOO_HOST 1
 #define RH_LOO_EXPECT_HOST 1
 #define RH_LOO_QUANTILE_HOST 1
@@ -22,6 +25,7 @@
 #include "device/rh_cov.hip.h"
 #include "device/rh_hist.hip.h"
 #include "device/rh_rank.hip.h"
+#include "device/rh_mcse.hip.h"
 #include "device/rh_loo.hip.h"
 #include "device/rh_loo_expect.hip.h"
 #include "device/rh_loo_quantile.hip.h"
@@ -176,6 +180,49 @@ inline Rank rank_plan(long long chains, long long count, long long K, long long 
   P.blocks = (P.S + RK_BLOCK - 1) / RK_BLOCK;
   P.tau_min = 1.0 / std::log10((double)P.S);
   return P;
+}
+// ---- Monte Carlo standard errors and ESS of the reported figures (device/rh_mcse.hip.h) ----
+struct Mcse {
+  long long h, M, S;             // as Rank's
+  int L, sl;                     // as Rank's
+  int nprobs, nseries;           // probabilities; series per column: MK_NFIXED + nprobs
+  long long per_col, pc;         // workspace bytes of one column (y, two key buffers, ws [nseries][M][sl]: no series buffer); columns per chunk
+  bool over_cap;                 // one column alone is beyond the cap
+  long long tiles, mtiles;       // as Rank's: the summary's plan of one flat chain of S values
+  int passes;
+  long long stiles;              // stage tiles of RK_ROWS flat values
+  long long chain_lds;           // the chain launch's dynamic LDS in bytes: MK_CHAIN_LDS(h) doubles
+  long long idx[MK_MAXPROBS];   // the quantiles' order statistics j_k (precis: floor(S * p)), as summary_plan computes idx
+  double tau_min;                // 1 / log10(S)
+  long long run(int k) const { return (long long)RS_TILE << k; }
+};
+// K: the selected columns; probs [nprobs], nprobs <= MK_MAXPROBS; cap: MK_WS_CAP_BYTES (a parameter for the CPU tests' driver, where small shapes make several chunks)
+inline Mcse mcse_plan(long long chains, long long count, long long K, const double *probs, int nprobs, long long cap = MK_WS_CAP_BYTES) {
+  Mcse P = {};
+  const Rank R = rank_plan(chains, count, K, cap);
+  P.h = R.h; P.M = R.M; P.S = R.S; P.L = R.L; P.sl = R.sl;
+  P.tiles = R.tiles; P.mtiles = R.mtiles; P.passes = R.passes; P.stiles = R.stiles; P.tau_min = R.tau_min;
+  P.nprobs = nprobs;
+  P.nseries = MK_NFIXED + nprobs;
+  P.chain_lds = 8 * (long long)MK_CHAIN_LDS(P.h);
+  P.per_col = 3 * P.S * 8 + (long long)P.nseries * P.M * P.sl * 8;
+  P.over_cap = P.per_col > cap;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_col, K));
+  const Summary Q = summary_plan(1, P.S, 1, 1, probs, nprobs, 0.0);
+  for (int k = 0; k < nprobs; k++) P.idx[k] = Q.idx[k];
+  return P;
+}
+// the order statistics whose half distance is the standard error of the quantile at probability p with effective sample size e:
+// the 16 % and 84 % points a, b of Beta(e p + 1, e (1 - p) + 1); i1 = max(floor(a S), 1) - 1, i2 = min(ceil(b S), S) - 1.
+// pick: j, i1, i2 (MK_NPICK); no ess (NaN, or not above 0): i1 = i2 = -1
+inline void mcse_pick(long long S, long long j, double p, double e, long long *pick) {
+  pick[0] = j; pick[1] = -1; pick[2] = -1;
+  if (!(e > 0.0) || !std::isfinite(e)) return;
+  const double sa = e * p + 1.0, sb = e * (1.0 - p) + 1.0;
+  const double a = rh_qbeta::qbeta(0.15865525393145707, sa, sb), b = rh_qbeta::qbeta(0.8413447460685429, sa, sb);
+  if (!(a == a) || !(b == b)) return;
+  pick[1] = std::max<long long>((long long)std::floor(a * (double)S), 1) - 1;
+  pick[2] = std::min<long long>((long long)std::ceil(b * (double)S), S) - 1;
 }
 // ---- pointwise WAIC and PSIS-LOO (device/rh_loo.hip.h) ----
 struct Loo {

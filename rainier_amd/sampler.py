@@ -679,6 +679,57 @@ def rank_diagnostics_device(ptr: int, chains: int, iterations: int, nvars: int, 
     return _rank_result(call, nvars, cols)
 
 
+class Mcse(NamedTuple):
+    """Monte Carlo standard errors and effective sample sizes of the reported figures (Vehtari et al. 2021, section 4) per selected
+    column: how many digits of mean, sd and quantile [K][nprobs] survive the Monte Carlo error.  mcse_sd is the delta method's (the
+    `posterior` package's form); mcse_quantile half the distance of the order statistics at the 16 % and 84 % points of
+    Beta(ess p + 1, ess (1 - p) + 1); acf [K][nlags + 1] the autocorrelations of the values (NaN beyond lag min(h - 1, 255));
+    truncated: bit 0 mean, bit 1 sd, bit 2 the squares behind mcse_sd, bit 3 + k quantile k -- where a bit is set the lags ran out at
+    255 before the autocorrelations did and that ESS is an upper bound."""
+    mean: np.ndarray
+    sd: np.ndarray
+    ess_mean: np.ndarray
+    ess_sd: np.ndarray
+    mcse_mean: np.ndarray
+    mcse_sd: np.ndarray
+    quantile: np.ndarray
+    ess_quantile: np.ndarray
+    mcse_quantile: np.ndarray
+    acf: np.ndarray
+    truncated: np.ndarray
+    cols: Tuple[int, ...]
+    probs: Tuple[float, ...]
+
+
+def _mcse_result(call, nvars, cols, probs, nlags, model=None):
+    """shared by Sampler.mcse and mcse_device: call(cols, ncols, probs, nprobs, nlags, the ten double outputs, truncated) -> rc"""
+    sel = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+    k = int(nvars) if sel is None else len(sel)
+    pr = np.ascontiguousarray([float(p) for p in probs], dtype=np.float64)
+    npr, nl = len(pr), int(nlags)
+    kk = max(k, 1)
+    six = [np.zeros(kk) for _ in range(6)]
+    three = [np.zeros((kk, npr)) for _ in range(3)]
+    acf = np.zeros((kk, max(nl, 0) + 1))
+    tr = np.zeros(kk, dtype=np.int32)
+    buf = sel if sel is None or k else np.zeros(1, dtype=np.int32)       # an empty list is a list (refused), not "all columns"
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _capi.check(call(ip(buf) if sel is not None else None, k if sel is not None else 0, _capi.dptr(pr) if npr else None, npr, nl,
+                     *[_capi.dptr(a) for a in six + three + [acf]], ip(tr)), model)
+    return Mcse(*[a[:k] for a in six + three + [acf, tr]], tuple(range(k)) if sel is None else tuple(sel.tolist()), tuple(pr.tolist()))
+
+
+def mcse_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
+                cols: Optional[Sequence[int]] = None, probs: Sequence[float] = (0.05, 0.5, 0.95), nlags: int = 0) -> Mcse:
+    """Monte Carlo standard errors and ESS of the mean, the sd and the quantiles at `probs` (at most 16) over the window
+    [first, first + count) (count >= 4, each chain split in two halves as for rank_diagnostics_device) of a device buffer
+    [chains][iterations][nvars], computed where the draws are (rh_mcse_device).  cols: the parameters asked for, in the result's
+    order (None: all); nlags (0 .. 255): the lags of the autocorrelation function returned with them."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_mcse_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count, *a)
+    return _mcse_result(call, nvars, cols, probs, nlags)
+
+
 class Loo(NamedTuple):
     """Pointwise WAIC and PSIS-LOO (Vehtari, Gelman, Gabry 2017) per selected observation: lpd, p_waic, elpd_waic = lpd - p_waic,
     elpd_loo, p_loo = lpd - elpd_loo, the Pareto shape pareto_k of the importance ratios' tail (above 0.7: that elpd_loo is not to be
@@ -1150,6 +1201,17 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_rank_diagnostics(self._h, int(first), count, *a)
         return _rank_result(call, self.model.nVars, cols, self.model._h)
+
+    def mcse(self, first: int = 0, count: Optional[int] = None, cols: Optional[Sequence[int]] = None, probs: Sequence[float] = (0.05, 0.5, 0.95),
+             nlags: int = 0) -> Mcse:
+        """How many digits of summary()'s figures survive the Monte Carlo error: the standard errors and effective sample sizes of the
+        mean, the sd and the quantiles at `probs` (Vehtari et al. 2021, section 4) of the parameters over the window
+        [first, first + count) of every chain, with the autocorrelations up to lag `nlags`, computed where the draws are
+        (rh_sampler_mcse).  cols: the parameters asked for, in the result's order (None: all); count = None: everything completed so
+        far.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_mcse(self._h, int(first), count, *a)
+        return _mcse_result(call, self.model.nVars, cols, probs, nlags, self.model._h)
 
     def loo(self, predictor: Predictor, first: int = 0, count: Optional[int] = None, thin: int = 1, cols: Optional[Sequence[int]] = None) -> Loo:
         """Which model predicts better: pointwise WAIC and PSIS-LOO (Vehtari, Gelman, Gabry 2017) of the predictor's requirements --
