@@ -46,7 +46,8 @@ extern "C" {
                                  rh_sampler_mcse, rh_mcse_device, rh_mcse_lower_only,
                                  rh_loo_device, rh_sampler_loo, rh_loo_lower_only,
                                  rh_loo_expect_device, rh_sampler_loo_expect, rh_loo_expect_lower_only,
-                                 rh_loo_quantile_device, rh_sampler_loo_quantile, rh_loo_quantile_lower_only) */
+                                 rh_loo_quantile_device, rh_sampler_loo_quantile, rh_loo_quantile_lower_only,
+                                 rh_sampler_joint_diagnostics, rh_joint_diagnostics_device, rh_joint_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -623,6 +624,47 @@ int rh_mcse_device(const void *dev_draws, int32_t device, int32_t chains, int32_
 /* No device needed: the standard error kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_mcse_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- joint convergence over device-resident draws: multivariate ESS and MPSRF ------------------------------------------------------
+ * Whether the chains know the parameters JOINTLY: every marginal R-hat can be near 1 while one linear combination has not mixed, and
+ * the smallest per-column ESS is not the number of independent draws of the vector.  The multivariate effective sample size (Vats,
+ * Flegal, Jones 2019; batch means replicated over the chains) and the multivariate potential scale reduction factor (Brooks and
+ * Gelman 1998), from three Gram matrices computed where the draws are (csrc/device/rh_joint.hip.h, fp64 matrix cores) and a K x K
+ * finish on the host (csrc/dense_sym.hpp: Cholesky, triangular solves, tridiagonal QL; O(K^3), hence K <= 256).
+ * Input: draws [chains C][iterations][nvars], the window [first, first + count) of every chain, count >= 4, no thinning; cols / ncols
+ * as for rh_covariance_device.  batch: the batch length b, 0: floor(sqrt(count)).  a = floor(count / b) batches per chain, a >= 2,
+ * n' = a b; the FIRST count - n' draws of every chain's window are dropped; N = C n'.
+ *   Ybar[c][k] = mean of batch k of chain c;  m[c] = mean of chain c's n' used rows;  mu = mean of the N used rows (the sums: batch,
+ *   then the batches of a chain in ascending k, then the chains in ascending c: their order depends on (C, count, b) alone);
+ *   W      = sum_c sum_t (x - m_c)(x - m_c)^T / (C (n' - 1));      Bn = sum_c (m_c - mu)(m_c - mu)^T / (C - 1)  (C = 1: NaN);
+ *   Sigma  = b sum_c sum_k (Ybar_ck - mu)(Ybar_ck - mu)^T / (C a - 1);
+ *   Lambda = ((double)(C (n' - 1)) * W + (double)(n' (C - 1)) * Bn) / (double)(N - 1), the pooled sample covariance by the ANOVA
+ *            identity, IEEE operations in that order on the finished W and Bn; C = 1: Lambda = W.
+ * Outputs, caller-allocated on the host, each may be NULL:
+ *   mess [1]  = N exp((log det Lambda - log det Sigma) / K);
+ *   mpsrf [1] = sqrt((n' - 1) / n' + (C + 1) / C * lambda_max(W^-1 Bn));
+ *   ess_bm [K]: N * Lambda_ii / Sigma_ii;  mean [K] = mu;  within [K][K] = W;  between [K][K] = Bn;  sigma [K][K] = Sigma;
+ *   mcse_cov [K][K] = Sigma / N, the covariance of the Monte Carlo error of `mean`;  plan [3] (int32) = b, a, count - n'.
+ * Every matrix is bitwise symmetric.  Not errors, RH_OK: mess is NaN where C a - 1 < K, mpsrf where C < 2 or C (n' - 1) < K, either
+ * where a Cholesky pivot is not finite and > 0 or the list names a column twice.  A NaN in a column makes that column's entry of mean
+ * and ess_bm, its row and column of every matrix and both scalars NaN, and touches nothing else.
+ * Deterministic: no floating-point atomics; a second call, a window and its copy, and any chunking give the same bits, and entry (i, j)
+ * of a call over a column list has the bits of entry (cols[i], cols[j]) of the call over all columns.
+ * RH_E_INVALID: a broken window, count < 4, batch < 0, a < 2, an index outside [0, nvars), ncols < 1 with a list.  RH_E_UNSUPPORTED,
+ * from the shape alone and before any launch: K > 256; one tile pair's partial sums beyond the 128 MiB workspace cap.  No device:
+ * RH_E_DEVICE (no CPU fallback).
+ * The sampler form goes to the sampler's stream behind its pending work, is not part of rh_timing and does not alter the chains. */
+int rh_sampler_joint_diagnostics(rh_sampler *s, int32_t first, int32_t count, int32_t batch, const int32_t *cols, int32_t ncols,
+                                 double *mess, double *mpsrf, double *ess_bm, double *mean, double *within, double *between,
+                                 double *sigma, double *mcse_cov, int32_t *plan);
+/* the same over any device buffer [chains][iterations][nvars] on `device` (-1: the current one); synchronises the device before and after */
+int rh_joint_diagnostics_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                                int32_t count, int32_t batch, const int32_t *cols, int32_t ncols, double *mess, double *mpsrf,
+                                double *ess_bm, double *mean, double *within, double *between, double *sigma, double *mcse_cov,
+                                int32_t *plan);
+/* No device needed: the joint diagnostics kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_joint_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 /* ---- pointwise WAIC and PSIS-LOO over device-resident log-likelihood draws --------------------------------------------------------
  * Which of two models predicts better (Vehtari, Gelman, Gabry 2017), computed where the draws are (csrc/device/rh_loo.hip.h).

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how long the batches and how many splits of the joint diagnostics' three Grams, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -8,6 +8,7 @@
 #include <cmath>
 
 #include "qbeta.hpp"
+#include "dense_sym.hpp"
 
 // the constants are the device headers' own: their block routines compile as plain C++ in host mode
 #define RH_TRACE_HOST 1
@@ -20,9 +21,11 @@
 #define RH_LOO_EXPECT_HOST 1
 #define RH_LOO_QUANTILE_HOST 1
 #define RH_PPC_HOST 1
+#define RH_JOINT_HOST 1
 #include "device/rh_trace.hip.h"
 #include "device/rh_summary.hip.h"
 #include "device/rh_cov.hip.h"
+#include "device/rh_joint.hip.h"
 #include "device/rh_hist.hip.h"
 #include "device/rh_rank.hip.h"
 #include "device/rh_mcse.hip.h"
@@ -90,6 +93,62 @@ inline Covariance covariance_plan(long long chains, long long count, long long t
   P.over_cap = P.per_pair > cap;
   P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, P.pairs));
   return P;
+}
+// ---- joint diagnostics: multivariate ESS and MPSRF (device/rh_joint.hip.h) ----
+struct Joint {
+  long long b, a, np, dropped, N;   // batch length; batches per chain; used draws per chain a b; the first count - np of a window are dropped; C np
+  long long R[3], S[3];             // flat rows and splits of RC_SPLIT of the three Grams: within (N), batch means (C a), between (C)
+  long long ctiles, pairs;          // column tiles of RC_TC; tile pairs bi <= bj, in rc_pair_of's order
+  long long per_pair, pc, chunks;   // workspace bytes of one tile pair (its S[0] + S[1] + S[2] partial tiles); tile pairs per chunk; chunks
+  bool over_cap;                    // one tile pair alone is beyond the cap
+};
+// batch: the batch length, 0: floor(sqrt(count)); K: the selected columns; cap: RC_WS_CAP_BYTES (a parameter for the CPU tests' driver)
+inline Joint joint_plan(long long chains, long long count, long long batch, long long K, long long cap = RC_WS_CAP_BYTES) {
+  Joint P = {};
+  P.b = batch > 0 ? batch : (long long)std::floor(std::sqrt((double)count));
+  while (P.b * P.b > count && batch <= 0) P.b--;                 // (the square root of a long long, whatever the libm)
+  while ((P.b + 1) * (P.b + 1) <= count && batch <= 0) P.b++;
+  P.b = std::max<long long>(P.b, 1);
+  P.a = count / P.b;
+  P.np = P.a * P.b;
+  P.dropped = count - P.np;
+  P.N = chains * P.np;
+  P.R[0] = P.N; P.R[1] = chains * P.a; P.R[2] = chains;
+  for (int g = 0; g < 3; g++) P.S[g] = (P.R[g] + RC_SPLIT - 1) / RC_SPLIT;
+  P.ctiles = (K + RC_TC - 1) / RC_TC;
+  P.pairs = P.ctiles * (P.ctiles + 1) / 2;
+  P.per_pair = RC_PAIR_BYTES(P.S[0] + P.S[1] + P.S[2]);
+  P.over_cap = P.per_pair > cap;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, P.pairs));
+  P.chunks = (P.pairs + P.pc - 1) / P.pc;
+  return P;
+}
+// The K x K finish on the host, from the finished matrices [K][K], the chains' means m [C][K] and mu [K] (any output may be NULL):
+//   mess = N exp((log det Lambda - log det Sigma) / K); NaN from the shape where C a - 1 < K (Sigma has no full rank);
+//   mpsrf = sqrt((n' - 1) / n' + (C + 1) / C * lambda_max(W^-1 Bn)); NaN from the shape where C < 2 or C (n' - 1) < K;
+//   either NaN where a Cholesky pivot is not finite and > 0, and where the list names a column twice (singular: `repeated`);
+//   ess_bm[i] = N * Lambda_ii / Sigma_ii, mcse_cov = Sigma / N, IEEE operations in that order.
+inline void joint_figures(const Joint &P, long long C, int K, bool repeated, const double *W, const double *Bn, const double *Sigma,
+                          const double *Lambda, const double *m, const double *mu, double *mess, double *mpsrf, double *ess_bm, double *mcse_cov) {
+  const double nan = std::nan(""), N = (double)P.N;
+  const size_t kk = (size_t)K * (size_t)K;
+  if (mess) {
+    *mess = nan;
+    if (!repeated && C * P.a - 1 >= K) {
+      std::vector<double> A(Lambda, Lambda + kk), B(Sigma, Sigma + kk);
+      double ll, ls;
+      if (rh_dense::cholesky(A.data(), K, &ll) && rh_dense::cholesky(B.data(), K, &ls)) *mess = N * std::exp((ll - ls) / (double)K);
+    }
+  }
+  if (mpsrf) {
+    *mpsrf = nan;
+    if (!repeated && C >= 2 && C * (P.np - 1) >= K) {
+      const double top = rh_dense::lambda_max_within_between(W, Bn, m, mu, (int)C, K);   // (m and mu are read where C - 1 < K only)
+      *mpsrf = std::sqrt((double)(P.np - 1) / (double)P.np + (double)(C + 1) / (double)C * top);
+    }
+  }
+  for (int i = 0; ess_bm && i < K; i++) ess_bm[i] = N * Lambda[(size_t)i * K + i] / Sigma[(size_t)i * K + i];
+  for (size_t e = 0; mcse_cov && e < kk; e++) mcse_cov[e] = Sigma[e] / N;
 }
 // ---- histograms and joint count grids (device/rh_hist.hip.h) ----
 struct Histogram {

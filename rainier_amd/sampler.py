@@ -730,6 +730,52 @@ def mcse_device(ptr: int, chains: int, iterations: int, nvars: int, device: int 
     return _mcse_result(call, nvars, cols, probs, nlags)
 
 
+class JointDiagnostics(NamedTuple):
+    """Whether the chains know the selected parameters jointly.  mess: the multivariate effective sample size (Vats, Flegal, Jones
+    2019), N (det Lambda / det Sigma)^(1/K) with Lambda the pooled sample covariance and Sigma the batch-means estimate, replicated
+    over the chains, of the asymptotic covariance of the Monte Carlo mean; mpsrf: the multivariate potential scale reduction factor
+    (Brooks and Gelman 1998); ess_bm [K]: the batch-means ESS per column, N Lambda_ii / Sigma_ii; mean [K]; within [K][K] (W),
+    between [K][K] (B / n'), sigma [K][K]; mcse_cov [K][K] = Sigma / N, the covariance of the Monte Carlo error of `mean`; batch (b),
+    batches (a per chain) and dropped (the first count - a b draws of every chain's window); cols.  mess is NaN where C a - 1 < K,
+    mpsrf where C < 2 or C (a b - 1) < K."""
+    mess: float
+    mpsrf: float
+    ess_bm: np.ndarray
+    mean: np.ndarray
+    within: np.ndarray
+    between: np.ndarray
+    sigma: np.ndarray
+    mcse_cov: np.ndarray
+    batch: int
+    batches: int
+    dropped: int
+    cols: Tuple[int, ...]
+
+
+def _joint_result(call, nvars, cols, batch, model=None):
+    """shared by Sampler.joint_diagnostics and joint_diagnostics_device: call(batch, cols, ncols, outputs ...) -> rc"""
+    sel = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+    k = int(nvars) if sel is None else len(sel)
+    scal, ess, mean, mats, plan = np.zeros(2), np.zeros(k), np.zeros(k), np.zeros((4, k, k)), np.zeros(3, dtype=np.int32)
+    buf = sel if sel is None or k else np.zeros(1, dtype=np.int32)       # an empty list is a list (refused), not "all columns"
+    ip = C.POINTER(C.c_int32)
+    _capi.check(call(int(batch), buf.ctypes.data_as(ip) if sel is not None else None, k if sel is not None else 0, _capi.dptr(scal[0:1]),
+                     _capi.dptr(scal[1:2]), _capi.dptr(ess), _capi.dptr(mean), *[_capi.dptr(mats[q]) for q in range(4)], plan.ctypes.data_as(ip)), model)
+    return JointDiagnostics(float(scal[0]), float(scal[1]), ess, mean, mats[0], mats[1], mats[2], mats[3], int(plan[0]), int(plan[1]), int(plan[2]),
+                            tuple(range(k)) if sel is None else tuple(sel.tolist()))
+
+
+def joint_diagnostics_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
+                             cols: Optional[Sequence[int]] = None, batch: int = 0) -> JointDiagnostics:
+    """Multivariate ESS and MPSRF over the window [first, first + count) (count >= 4, no thinning) of a device buffer
+    [chains][iterations][nvars] (a sampler's draws, a predictor's to_host = False result, Comm.allgather_draws(to_host=False)),
+    computed where the draws are (rh_joint_diagnostics_device).  cols: the parameters asked for, in the result's order (None: all; at
+    most 256); batch: the batch length (0: floor(sqrt(count)))."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_joint_diagnostics_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count, *a)
+    return _joint_result(call, nvars, cols, batch)
+
+
 class Loo(NamedTuple):
     """Pointwise WAIC and PSIS-LOO (Vehtari, Gelman, Gabry 2017) per selected observation: lpd, p_waic, elpd_waic = lpd - p_waic,
     elpd_loo, p_loo = lpd - elpd_loo, the Pareto shape pareto_k of the importance ratios' tail (above 0.7: that elpd_loo is not to be
@@ -1212,6 +1258,17 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_mcse(self._h, int(first), count, *a)
         return _mcse_result(call, self.model.nVars, cols, probs, nlags, self.model._h)
+
+    def joint_diagnostics(self, first: int = 0, count: Optional[int] = None, cols: Optional[Sequence[int]] = None, batch: int = 0) -> JointDiagnostics:
+        """Can this run be trusted for the parameters jointly: the multivariate effective sample size (Vats, Flegal, Jones 2019) and
+        the multivariate potential scale reduction factor (Brooks and Gelman 1998) over the window [first, first + count) of every
+        chain, computed where the draws are (rh_sampler_joint_diagnostics).  Per-column figures can all look fine while one linear
+        combination of the parameters has not mixed; these two see it.  cols: the parameters asked for, in the result's order (None:
+        all; at most 256); batch: the batch length (0: floor(sqrt(count))); count = None: everything completed so far.  The chains are
+        not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_joint_diagnostics(self._h, int(first), count, *a)
+        return _joint_result(call, self.model.nVars, cols, batch, self.model._h)
 
     def loo(self, predictor: Predictor, first: int = 0, count: Optional[int] = None, thin: int = 1, cols: Optional[Sequence[int]] = None) -> Loo:
         """Which model predicts better: pointwise WAIC and PSIS-LOO (Vehtari, Gelman, Gabry 2017) of the predictor's requirements --
