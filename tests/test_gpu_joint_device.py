@@ -49,6 +49,32 @@ def test_device_window_batch_and_column_list():
         assert same_bits(getattr(sub, q), getattr(full, q)[np.ix_(cols, cols)]), q
 
 
+def test_device_repeated_out_of_order_column_list_in_every_family_that_takes_one():
+    """cols = [2, 0, 2] over 4 chains x 32 iterations x 3 parameters through the six calls that take a column list (covariance,
+    histogram, rank diagnostics, standard errors, joint diagnostics, WAIC / PSIS-LOO): entry k of every per-column result has the bits
+    of the call that asks for column cols[k] alone -- in the matrices, entry (k, k)."""
+    x = fixture(4, 32, 3)
+    cols = [2, 0, 2]
+    calls = {
+        "covariance": (lambda c: R.covariance_device(d.ptr.value, 4, 32, 3, device=0, cols=c, corr=True), ("mean",), ("cov", "corr")),
+        "histogram": (lambda c: R.histogram_device(d.ptr.value, 4, 32, 3, device=0, cols=c, bins=7), ("edges", "counts", "under", "over", "nan"), ()),
+        "rank": (lambda c: R.rank_diagnostics_device(d.ptr.value, 4, 32, 3, device=0, cols=c), ("rhat_bulk", "rhat_folded", "ess_bulk", "ess_tail", "truncated"), ()),
+        "mcse": (lambda c: R.mcse_device(d.ptr.value, 4, 32, 3, device=0, cols=c, nlags=3),
+                 ("mean", "sd", "ess_mean", "ess_sd", "mcse_mean", "mcse_sd", "quantile", "ess_quantile", "mcse_quantile", "acf", "truncated"), ()),
+        "joint": (lambda c: on_device(d, cols=c), ("mean",), MATS),
+        "loo": (lambda c: R.loo_device(d.ptr.value, 4, 32, 3, device=0, cols=c), ("lpd", "p_waic", "elpd_loo", "pareto_k", "tail_n"), ()),
+    }
+    with DeviceDraws(x) as d:
+        for family, (call, per_column, matrices) in calls.items():
+            got = call(cols)
+            alone = {c: call([c]) for c in set(cols)}
+            for k, c in enumerate(cols):
+                for q in per_column:
+                    assert same_bits(np.asarray(getattr(got, q))[k], np.asarray(getattr(alone[c], q))[0]), (family, q, k)
+                for q in matrices:
+                    assert same_bits(np.asarray(getattr(got, q))[k, k], np.asarray(getattr(alone[c], q))[0, 0]), (family, q, k)
+
+
 def test_sampler_joint_diagnostics_linreg():
     spec = models.linreg(n=2000, k=3)
     m = R.Model(spec, device=0, math_mode=_capi.MATH_STRICT)
