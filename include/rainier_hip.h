@@ -47,7 +47,8 @@ extern "C" {
                                  rh_loo_device, rh_sampler_loo, rh_loo_lower_only,
                                  rh_loo_expect_device, rh_sampler_loo_expect, rh_loo_expect_lower_only,
                                  rh_loo_quantile_device, rh_sampler_loo_quantile, rh_loo_quantile_lower_only,
-                                 rh_sampler_joint_diagnostics, rh_joint_diagnostics_device, rh_joint_lower_only) */
+                                 rh_sampler_joint_diagnostics, rh_joint_diagnostics_device, rh_joint_lower_only,
+                                 rh_sampler_rank_plot, rh_rank_plot_device, rh_rank_plot_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -583,6 +584,32 @@ int rh_rank_diagnostics_device(const void *dev_draws, int32_t device, int32_t ch
 /* No device needed: the rank diagnostics kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_rank_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- rank plots over device-resident draws: per-chain rank counts -----------------------------------------------------------------
+ * Vehtari et al. (2021), section 4.1: which chain is off, and how.  A parameter's draws are pooled over all chains and ranked; each
+ * chain's ranks are binned.  With good mixing every chain's counts are level; a chain stuck elsewhere, a chain of another scale or a
+ * chain with a trend shows as a slope, a cup or a cap.  Computed where the draws are (csrc/device/rh_rank_plot.hip.h): one pooled sort
+ * per column, then one pass that ranks every value against splitters in LDS and a short run of the sorted column.
+ * Input: draws [chains][iterations][nvars], the window [first, first + count) of every chain, count >= 1, unsplit, no thinning; cols /
+ * ncols as for the rank diagnostics.  C = chains, n = count, S = C n values per column; 2 <= bins <= 1024.
+ * Order: Double.compare's (-0.0 before +0.0), the summaries' key order; infinities are ordinary values.  For the value of (chain c,
+ * iteration i): L pooled keys below it, U at or below it, r2 = L + U + 1 (twice the average rank; ties share it),
+ *   bin = ((r2 - 1) * bins) / (2 S)  in 64-bit integer division  (floor(u bins), u = (r - 1/2) / S; 0 <= bin < bins).
+ * Outputs, caller-allocated on the host: counts [K][chains][bins], each chain's row summing to n; nan [K], the NaN values of the
+ * column's window.  A column with nan[k] > 0 has all its counts 0.  Integers: the same on every call, for a window and its copy, for
+ * any chunking of the columns.
+ * Workspace: 24 S bytes per column, the columns in chunks below 128 MiB; one column alone beyond it is refused with RH_E_UNSUPPORTED
+ * from the shape alone, before any launch.  A broken window, count < 1, bins outside 2 .. 1024, an index outside [0, nvars), ncols < 1
+ * with a list, a NULL output: RH_E_INVALID.  No device: RH_E_DEVICE (no CPU fallback).
+ * The sampler form goes to the sampler's stream behind its pending work, is not part of rh_timing and does not alter the chains. */
+int rh_sampler_rank_plot(rh_sampler *s, int32_t first, int32_t count, const int32_t *cols, int32_t ncols, int32_t bins, int64_t *counts,
+                         int64_t *nan);
+/* the same over any device buffer [chains][iterations][nvars] on `device` (-1: the current one); synchronises the device before and after */
+int rh_rank_plot_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                        int32_t count, const int32_t *cols, int32_t ncols, int32_t bins, int64_t *counts, int64_t *nan);
+/* No device needed: the rank plot kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_rank_plot_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 /* ---- Monte Carlo standard errors and ESS of the reported figures over device-resident draws ------------------------------------------
  * How many digits of a mean, an sd or a quantile survive the Monte Carlo error (Vehtari et al. 2021, section 4), computed where the

@@ -42,6 +42,8 @@ EXPORTS = [
     "rh_sampler_histogram", "rh_histogram_device", "rh_histogram_lower_only",
     # rank-normalised split R-hat, bulk and tail ESS over device-resident draws (Vehtari et al. 2021)
     "rh_sampler_rank_diagnostics", "rh_rank_diagnostics_device", "rh_rank_lower_only",
+    # rank plots: per-chain rank counts over device-resident draws (Vehtari et al. 2021, section 4.1)
+    "rh_sampler_rank_plot", "rh_rank_plot_device", "rh_rank_plot_lower_only",
     # Monte Carlo standard errors and ESS of the mean, the sd and quantiles over device-resident draws (Vehtari et al. 2021, section 4)
     "rh_sampler_mcse", "rh_mcse_device", "rh_mcse_lower_only",
     # multivariate ESS (Vats, Flegal, Jones 2019) and MPSRF (Brooks and Gelman 1998) over device-resident draws
@@ -184,6 +186,9 @@ def lib():
     L.rh_sampler_rank_diagnostics.argtypes = [vp, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_rank_diagnostics_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_rank_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_sampler_rank_plot.argtypes = [vp, i32, i32, ip, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rh_rank_plot_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, ip, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rh_rank_plot_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_sampler_mcse.argtypes = [vp, i32, i32, ip, i32, dp, i32, i32] + [dp] * 10 + [ip]
     L.rh_mcse_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, ip, i32, dp, i32, i32] + [dp] * 10 + [ip]
     L.rh_mcse_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -413,6 +418,18 @@ def rank_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_rank_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def rank_plot_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_rank_plot.hip.h behind rh_summary.hip.h (rank plots on the device: per-chain rank counts) -> code object for
+    `arch`, without a device: compiled through the kernel cache and judged as before a launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_rank_plot_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

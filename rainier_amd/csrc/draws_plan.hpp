@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how long the batches and how many splits of the joint diagnostics' three Grams, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how long the batches and how many splits of the joint diagnostics' three Grams, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how many segments of a chain and which splitter stride of the rank plots, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -16,6 +16,7 @@
 #define RH_COV_HOST 1
 #define RH_HIST_HOST 1
 #define RH_RANK_HOST 1
+#define RH_RANK_PLOT_HOST 1
 #define RH_MCSE_HOST 1
 #define RH_LOO_HOST 1
 #define RH_LOO_EXPECT_HOST 1
@@ -28,6 +29,7 @@
 #include "device/rh_joint.hip.h"
 #include "device/rh_hist.hip.h"
 #include "device/rh_rank.hip.h"
+#include "device/rh_rank_plot.hip.h"
 #include "device/rh_mcse.hip.h"
 #include "device/rh_loo.hip.h"
 #include "device/rh_loo_expect.hip.h"
@@ -238,6 +240,42 @@ inline Rank rank_plan(long long chains, long long count, long long K, long long 
   P.stiles = (P.S + RK_ROWS - 1) / RK_ROWS;
   P.blocks = (P.S + RK_BLOCK - 1) / RK_BLOCK;
   P.tau_min = 1.0 / std::log10((double)P.S);
+  return P;
+}
+// ---- rank plots: per-chain rank counts (device/rh_rank_plot.hip.h) ----
+struct RankPlot {
+  long long S;                   // values of one column: chains * count, unsplit
+  long long per_col, pc;         // workspace bytes of one column (y and two key buffers); columns per chunk
+  bool over_cap;                 // one column alone is beyond the cap
+  long long tiles, mtiles;       // tile sorts and merge workgroups per column: the summary's plan of one flat chain of S values
+  int passes;                    // merge passes; pass k merges runs of run(k) keys
+  long long stiles;              // stage tiles of RU_ROWS flat values
+  long long segs, seg_len;       // segments per chain of the count launch; iterations of a segment (the last one of a chain: the rest)
+  int shift;                     // log2 of the splitter stride: the smallest with ceil(S >> shift) <= RU_MAXSPLIT
+  long long stride, nsplit;      // 1 << shift; splitters of one column, ceil(S / stride)
+  long long lds_bytes;           // the count launch's dynamic LDS: the splitters and the bins
+  long long run(int k) const { return (long long)RS_TILE << k; }
+};
+// K: the selected columns; cap: RU_WS_CAP_BYTES (a parameter for the CPU tests' driver, where small shapes make several chunks).
+// A chain is cut where the chunk's columns x chains alone are fewer than RU_TARGET_WGS workgroups, into segments of at least RU_SEG_MIN.
+inline RankPlot rank_plot_plan(long long chains, long long count, long long K, int bins, long long cap = RU_WS_CAP_BYTES) {
+  RankPlot P = {};
+  P.S = chains * count;
+  P.per_col = 24 * std::min(P.S, 0x7fffffffffffffffll / 24);   // (saturated: 2^31 chains of 2^31 draws are beyond 64 bits of bytes)
+  P.over_cap = P.per_col > cap;
+  P.pc = 1;
+  if (P.over_cap) return P;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_col, K));
+  const Summary Q = summary_plan(1, P.S, 1, 1, nullptr, 0, 0.0);
+  P.tiles = Q.tiles; P.mtiles = Q.mtiles; P.passes = Q.passes;
+  P.stiles = (P.S + RU_ROWS - 1) / RU_ROWS;
+  const long long want = (RU_TARGET_WGS + P.pc * chains - 1) / (P.pc * chains), most = std::max<long long>(1, count / RU_SEG_MIN);
+  P.seg_len = (count + std::min(want, most) - 1) / std::min(want, most);
+  P.segs = (count + P.seg_len - 1) / P.seg_len;
+  while (((P.S + (1ll << P.shift) - 1) >> P.shift) > RU_MAXSPLIT) P.shift++;
+  P.stride = 1ll << P.shift;
+  P.nsplit = (P.S + P.stride - 1) >> P.shift;
+  P.lds_bytes = RU_LDS_BYTES(P.nsplit, bins);
   return P;
 }
 // ---- Monte Carlo standard errors and ESS of the reported figures (device/rh_mcse.hip.h) ----

@@ -679,6 +679,52 @@ def rank_diagnostics_device(ptr: int, chains: int, iterations: int, nvars: int, 
     return _rank_result(call, nvars, cols)
 
 
+class RankPlot(NamedTuple):
+    """Rank plots (Vehtari et al. 2021, section 4.1) per selected column: counts [K][chains][bins], how many of a chain's draws have
+    their pooled rank in each bin -- level where the chains mix; a chain stuck elsewhere, of another scale or with a trend shows as a
+    slope, a cup or a cap.  ecdf_gap [K][chains][bins]: the chain's ECDF of the normalised ranks at the bins' upper edges less the
+    uniform one's (the ECDF-difference plot of Saeilynoja, Buerkner, Vehtari 2022); ks [K][chains]: its largest magnitude; chi2
+    [K][chains]: Pearson's statistic of the counts against level ones.  nan [K]: the NaN values of the column's window; where it is not
+    0 the counts are 0 and the figures NaN.  Simultaneous confidence bands are not given: their calibration for autocorrelated chains
+    is a question of its own."""
+    counts: np.ndarray
+    ecdf_gap: np.ndarray
+    ks: np.ndarray
+    chi2: np.ndarray
+    nan: np.ndarray
+    cols: Tuple[int, ...]
+    bins: int
+
+
+def _rank_plot_result(call, chains, n, nvars, cols, bins, model=None):
+    """shared by Sampler.rank_plot and rank_plot_device: call(cols, ncols, bins, counts, nan) -> rc; the derived figures in float64"""
+    sel = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+    k, c, b = int(nvars) if sel is None else len(sel), max(int(chains), 0), min(max(int(bins), 0), 1025)   # (beyond 2 .. 1024 stays beyond it, within an int32: refused below)
+    counts, nan = np.zeros((k, c, b), dtype=np.int64), np.zeros(max(k, 1), dtype=np.int64)
+    buf = sel if sel is None or k else np.zeros(1, dtype=np.int32)       # an empty list is a list (refused), not "all columns"
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    _capi.check(call(buf.ctypes.data_as(C.POINTER(C.c_int32)) if sel is not None else None, k if sel is not None else 0, b, lp(counts), lp(nan)), model)
+    nan = nan[:k]
+    # from exact integers (below 2^53 at any allowed shape), so that a small gap keeps its digits: cum / n - (j + 1) / b = (cum b - (j + 1) n) / (n b)
+    nb = float(n * b)
+    gap = (np.cumsum(counts, axis=2) * b - np.arange(1, b + 1, dtype=np.int64) * n) / nb
+    chi2 = ((counts * b - n).astype(np.float64) ** 2).sum(axis=2) / nb          # sum (counts - n / b)^2 / (n / b)
+    bad = nan > 0
+    gap[bad], chi2[bad] = np.nan, np.nan
+    return RankPlot(counts, gap, np.abs(gap).max(axis=2), chi2, nan, tuple(range(k)) if sel is None else tuple(sel.tolist()), b)
+
+
+def rank_plot_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
+                     cols: Optional[Sequence[int]] = None, bins: int = 20) -> RankPlot:
+    """Which chain is off, and how: per-chain counts of the pooled ranks over the window [first, first + count) (count >= 1, the chains
+    unsplit) of a device buffer [chains][iterations][nvars] (a sampler's draws, a predictor's to_host = False result,
+    Comm.allgather_draws(to_host=False)), computed where the draws are (rh_rank_plot_device).  cols: the parameters asked for, in the
+    result's order (None: all); bins: 2 .. 1024.  Only the counts come back; RankPlot's other figures are derived from them here."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_rank_plot_device(C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count, *a)
+    return _rank_plot_result(call, chains, count, nvars, cols, bins)
+
+
 class Mcse(NamedTuple):
     """Monte Carlo standard errors and effective sample sizes of the reported figures (Vehtari et al. 2021, section 4) per selected
     column: how many digits of mean, sd and quantile [K][nprobs] survive the Monte Carlo error.  mcse_sd is the delta method's (the
@@ -1247,6 +1293,16 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_rank_diagnostics(self._h, int(first), count, *a)
         return _rank_result(call, self.model.nVars, cols, self.model._h)
+
+    def rank_plot(self, first: int = 0, count: Optional[int] = None, cols: Optional[Sequence[int]] = None, bins: int = 20) -> RankPlot:
+        """Which chain is off, and how: the rank plot (Vehtari et al. 2021, section 4.1) of the parameters over the window
+        [first, first + count) of every chain, unsplit -- per chain, the counts of its draws' pooled ranks in `bins` bins, with the
+        ECDF gaps, their largest magnitude and the chi-square statistic derived from them -- computed where the draws are
+        (rh_sampler_rank_plot).  cols: the parameters asked for, in the result's order (None: all); count = None: everything completed
+        so far.  Simultaneous confidence bands are not given.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_rank_plot(self._h, int(first), count, *a)
+        return _rank_plot_result(call, self.chains, count, self.model.nVars, cols, bins, self.model._h)
 
     def mcse(self, first: int = 0, count: Optional[int] = None, cols: Optional[Sequence[int]] = None, probs: Sequence[float] = (0.05, 0.5, 0.95),
              nlags: int = 0) -> Mcse:
