@@ -48,7 +48,8 @@ extern "C" {
                                  rh_loo_expect_device, rh_sampler_loo_expect, rh_loo_expect_lower_only,
                                  rh_loo_quantile_device, rh_sampler_loo_quantile, rh_loo_quantile_lower_only,
                                  rh_sampler_joint_diagnostics, rh_joint_diagnostics_device, rh_joint_lower_only,
-                                 rh_sampler_rank_plot, rh_rank_plot_device, rh_rank_plot_lower_only) */
+                                 rh_sampler_rank_plot, rh_rank_plot_device, rh_rank_plot_lower_only,
+                                 rh_sampler_kde, rh_kde_device, rh_sampler_kde_pairs, rh_kde_pairs_device, rh_kde_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -543,6 +544,47 @@ int rh_histogram2d_device(const void *dev_draws, int32_t device, int32_t chains,
 /* No device needed: the histogram kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_histogram_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- Gaussian kernel density estimates over device-resident draws: curves and surfaces ------------------------------------------------
+ * The smooth density of a parameter on a grid of points, and of a pair of parameters on a grid of points x points (the reference's
+ * contour, rainier-notebook package.scala:93-98), computed where the draws are (csrc/device/rh_kde.hip.h); only the curve or the
+ * surface comes back.  Bandwidths and bounds are the caller's (the Python layer has Silverman's and Scott's rules).
+ * Input: draws [chains][iterations][nvars]; window, thinning, flat rows and column lists are the covariance's: kept = ceil(count /
+ * thin), N = chains * kept, flat row r = c * kept + j is draw (c, first + j * thin); cols may repeat, NULL: all columns (K = nvars).
+ * A split is 4096 consecutive flat rows, S = ceil(N / 4096).
+ * Curves: npoints = G, 2 <= G <= 4096; range [K][2] = (lo, hi), finite with lo <= hi; bw [K] = h, finite and > 0; all required.
+ *   grid [K][G], built on the host in double: g[0] = lo, g[G-1] = hi, g[i] = lo + ((double)i * (hi - lo)) / (double)(G - 1);
+ *   z = (g[i] - x[r]) / h; term = exp(-0.5 * z * z), IEEE operations in that order, exp being fdlibm's e_exp (the same text on the
+ *   host and on the device); P_s[i] = one accumulator from +0.0, r ascending in split s, plain adds;
+ *   density[k][i] = (sum over s ascending of P_s[i]) / ((double)N * h * sqrt(2 pi)).
+ * Surfaces: pairs [P][2] = (a, b), a == b allowed; 2 <= npx, npy <= 256; range [P][2][2] = ((xlo, xhi), (ylo, yhi)); bw [P][2] =
+ *   (hx, hy); xgrid [P][npx], ygrid [P][npy] by the same formula per axis; phix[i][r] = exp(-0.5 * zx * zx) with zx = (gx[i] - a[r])
+ *   / hx, phiy[j][r] likewise from b, gy, hy; P_s[i][j] = one accumulator from +0.0, r ascending in split s: acc = fma(phix[i][r],
+ *   phiy[j][r], acc) -- a matrix product on the fp64 matrix cores, 128 N exponentials per 64 x 64 tile instead of 4096 N; the rows past N of a ragged group of
+ *   four are staged as +0.0; density[p][i][j] = (sum over s ascending of P_s[i][j]) / ((double)N * 2 pi * hx * hy).
+ * No special cases: a +-inf draw contributes +0.0; a NaN draw makes that column's whole curve (in either coordinate: that pair's
+ * whole surface) NaN and touches nothing else; a constant column is an ordinary input.  Nothing depends on the tiling, the chunking,
+ * the order of the column list or the launch: entry k of a call over cols has the bits of entry cols[k] of the call over all columns
+ * at the same range and bw.  Outputs are caller-allocated on the host.
+ * Workspace: the partial sums, S G 8 bytes per column resp. S 32 KiB per 64 x 64 tile of a surface, in chunks below 128 MiB; a shape
+ * whose single column or tile is beyond it is refused with RH_E_UNSUPPORTED from the shape alone, before any launch.  A NULL argument,
+ * a broken window, N < 1, npoints / npx / npy out of range, an index outside [0, nvars), bounds or a bandwidth as not allowed above:
+ * RH_E_INVALID, the message names the argument.  No device: RH_E_DEVICE (no CPU fallback).
+ * The sampler forms go to the sampler's stream behind its pending work, are not part of rh_timing and do not alter the chains. */
+int rh_sampler_kde(rh_sampler *s, int32_t first, int32_t count, int32_t thin, const int32_t *cols, int32_t ncols, int32_t npoints,
+                   const double *range, const double *bw, double *grid, double *density);
+int rh_sampler_kde_pairs(rh_sampler *s, int32_t first, int32_t count, int32_t thin, const int32_t *pairs, int32_t npairs, int32_t npx,
+                         int32_t npy, const double *range, const double *bw, double *xgrid, double *ygrid, double *density);
+/* the same over any device buffer [chains][iterations][nvars] on `device` (-1: the current one); synchronise the device before and after */
+int rh_kde_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first, int32_t count,
+                  int32_t thin, const int32_t *cols, int32_t ncols, int32_t npoints, const double *range, const double *bw, double *grid,
+                  double *density);
+int rh_kde_pairs_device(const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                        int32_t count, int32_t thin, const int32_t *pairs, int32_t npairs, int32_t npx, int32_t npy, const double *range,
+                        const double *bw, double *xgrid, double *ygrid, double *density);
+/* No device needed: the kernel density kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_kde_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 /* ---- rank-normalised split R-hat, bulk ESS and tail ESS over device-resident draws ----------------------------------------------
  * Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021), computed where the draws are (csrc/device/rh_rank.hip.h).  rh_diagnostics

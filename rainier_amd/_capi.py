@@ -40,6 +40,8 @@ EXPORTS = [
     "rh_sampler_covariance", "rh_covariance_device", "rh_covariance_lower_only",
     # histograms / joint count grids over device-resident draws (rainier-notebook package.scala:63-98)
     "rh_sampler_histogram", "rh_histogram_device", "rh_histogram_lower_only",
+    # Gaussian kernel density estimates over device-resident draws: curves and surfaces
+    "rh_sampler_kde", "rh_kde_device", "rh_sampler_kde_pairs", "rh_kde_pairs_device", "rh_kde_lower_only",
     # rank-normalised split R-hat, bulk and tail ESS over device-resident draws (Vehtari et al. 2021)
     "rh_sampler_rank_diagnostics", "rh_rank_diagnostics_device", "rh_rank_lower_only",
     # rank plots: per-chain rank counts over device-resident draws (Vehtari et al. 2021, section 4.1)
@@ -186,6 +188,11 @@ def lib():
     L.rh_sampler_rank_diagnostics.argtypes = [vp, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_rank_diagnostics_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, ip, i32, dp, dp, dp, dp, ip]
     L.rh_rank_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_sampler_kde.argtypes = [vp, i32, i32, i32, ip, i32, i32, dp, dp, dp, dp]
+    L.rh_kde_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ip, i32, i32, dp, dp, dp, dp]
+    L.rh_sampler_kde_pairs.argtypes = [vp, i32, i32, i32, ip, i32, i32, i32, dp, dp, dp, dp, dp]
+    L.rh_kde_pairs_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ip, i32, i32, i32, dp, dp, dp, dp, dp]
+    L.rh_kde_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rh_sampler_rank_plot.argtypes = [vp, i32, i32, ip, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rh_rank_plot_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, ip, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rh_rank_plot_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -418,6 +425,19 @@ def rank_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_rank_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def kde_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_kde.hip.h behind rh_cov.hip.h (kernel density estimates on the device: curves, and surfaces on the fp64 matrix
+    cores) -> code object for `arch`, without a device: compiled through the kernel cache and judged as before a launch (no spills, no
+    scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_kde_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

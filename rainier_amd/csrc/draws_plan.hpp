@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how long the batches and how many splits of the joint diagnostics' three Grams, how many column tiles and edges of a histogram, how many columns and lags of the rank diagnostics, how many segments of a chain and which splitter stride of the rank plots, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how long the batches and how many splits of the joint diagnostics' three Grams, how many column tiles and edges of a histogram, how many grid tiles, surface tiles and chunks of a kernel density estimate, how many columns and lags of the rank diagnostics, how many segments of a chain and which splitter stride of the rank plots, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -15,6 +15,7 @@
 #define RH_SUMMARY_HOST 1
 #define RH_COV_HOST 1
 #define RH_HIST_HOST 1
+#define RH_KDE_HOST 1
 #define RH_RANK_HOST 1
 #define RH_RANK_PLOT_HOST 1
 #define RH_MCSE_HOST 1
@@ -28,6 +29,7 @@
 #include "device/rh_cov.hip.h"
 #include "device/rh_joint.hip.h"
 #include "device/rh_hist.hip.h"
+#include "device/rh_kde.hip.h"
 #include "device/rh_rank.hip.h"
 #include "device/rh_rank_plot.hip.h"
 #include "device/rh_mcse.hip.h"
@@ -208,6 +210,55 @@ inline void histogram_edges(double lo, double hi, int nbins, double *e) {
   e[0] = lo;
   for (int i = 1; i < nbins; i++) e[i] = std::min(hi, std::max(e[i - 1], lo + ((double)i * w) / (double)nbins));
   e[nbins] = hi;
+}
+// ---- kernel density estimates, curves and surfaces (device/rh_kde.hip.h) ----
+// a * b for a, b >= 0, saturated at the largest long long (2^31 chains of 2^31 draws times a grid are beyond 64 bits of bytes)
+inline long long kde_sat_mul(long long a, long long b) { return b != 0 && a > 0x7fffffffffffffffll / b ? 0x7fffffffffffffffll : a * b; }
+struct Kde {
+  long long kept, N, S;          // kept iterations per chain; flat rows; splits of RC_SPLIT rows
+  long long gtiles;              // tiles of RKD_GT grid points
+  long long per_col, pc;         // workspace bytes of one column (its S partial curves); columns per chunk
+  bool over_cap;                 // one column alone is beyond the cap
+};
+// K: the selected columns; G: the points of a curve; cap: RKD_WS_CAP_BYTES (a parameter for the CPU tests' driver, where small shapes make several chunks)
+inline Kde kde_plan(long long chains, long long count, long long thin, long long K, int G, long long cap = RKD_WS_CAP_BYTES) {
+  Kde P = {};
+  P.kept = (count + thin - 1) / thin;
+  P.N = chains * P.kept;
+  P.S = (P.N + RC_SPLIT - 1) / RC_SPLIT;
+  P.gtiles = ((long long)G + RKD_GT - 1) / RKD_GT;
+  P.per_col = kde_sat_mul(P.S, (long long)G * 8);
+  P.over_cap = P.per_col > cap;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / std::max<long long>(P.per_col, 1), K));
+  return P;
+}
+struct KdePairs {
+  long long kept, N, S;          // as above
+  long long tx, ty, units;       // tiles of RC_TC points along x and y; units (pair x tile) in rkd_unit_of's order
+  long long per_unit, uc;        // workspace bytes of one unit (its S partial tiles); units per chunk
+  bool over_cap;                 // one unit alone is beyond the cap
+};
+inline KdePairs kde_pairs_plan(long long chains, long long count, long long thin, long long npairs, int npx, int npy, long long cap = RKD_WS_CAP_BYTES) {
+  KdePairs P = {};
+  P.kept = (count + thin - 1) / thin;
+  P.N = chains * P.kept;
+  P.S = (P.N + RC_SPLIT - 1) / RC_SPLIT;
+  P.tx = ((long long)npx + RC_TC - 1) / RC_TC;
+  P.ty = ((long long)npy + RC_TC - 1) / RC_TC;
+  P.units = npairs * P.tx * P.ty;
+  P.per_unit = kde_sat_mul(P.S, RKD_UNIT_BYTES(1));
+  P.over_cap = P.per_unit > cap;
+  P.uc = std::max<long long>(1, std::min<long long>(cap / std::max<long long>(P.per_unit, 1), P.units));
+  return P;
+}
+// bounds and a bandwidth as the calls take them
+inline bool kde_range_ok(const double *range) { return std::isfinite(range[0]) && std::isfinite(range[1]) && range[0] <= range[1]; }
+inline bool kde_bw_ok(double h) { return std::isfinite(h) && h > 0.0; }
+// g [G] from the bounds, in double: the ends are the bounds themselves
+inline void kde_grid(double lo, double hi, int G, double *g) {
+  g[0] = lo;
+  for (int i = 1; i < G - 1; i++) g[i] = lo + ((double)i * (hi - lo)) / (double)(G - 1);
+  g[G - 1] = hi;
 }
 // ---- rank-normalised split R-hat, bulk and tail ESS (device/rh_rank.hip.h) ----
 struct Rank {

@@ -640,6 +640,113 @@ def _histogram2d_result(call, pairs, bins, rng, model=None):
     return Histogram2d(tuple((int(a), int(b)) for a, b in pr), xe, ye, grid, outside)
 
 
+class Kde(NamedTuple):
+    """The smooth density of single parameters: for column k (parameter cols[k]) grid [K][G] (lo .. hi, evenly spaced), density
+    [K][G] (the Gaussian kernel density estimate at the grid's points; all NaN for a column that holds a NaN) and the bandwidths bw
+    [K] it was computed at."""
+    cols: Tuple[int, ...]
+    grid: np.ndarray
+    density: np.ndarray
+    bw: np.ndarray
+
+
+class KdePairs(NamedTuple):
+    """The smooth joint density of pairs of parameters (the reference's contour, rainier-notebook package.scala:93-98): for pair p =
+    (a, b) xgrid [P][npx], ygrid [P][npy], density [P][npx][npy] (a product Gaussian kernel; density[p][i][j] is at (xgrid[p][i],
+    ygrid[p][j])) and the bandwidths bw [P][2] = (hx, hy)."""
+    pairs: Tuple[Tuple[int, int], ...]
+    xgrid: np.ndarray
+    ygrid: np.ndarray
+    density: np.ndarray
+    bw: np.ndarray
+
+
+def _kde_rules(bw, rng, cut, n, d, columns, figures, what):
+    """Bandwidths [E] and bounds [E][2] of the entries over `columns` [E] (a curve's column; either axis of a pair).  bw: a rule's name
+    or an array [E]; rng: None or an array [E][2] with NaN for an automatic bound.  figures() -> (sd [nvars], q [nvars][4]) of one
+    summary call at probs (0, 0.25, 0.75, 1) over the same window, made only where a rule or an automatic bound needs it.
+    "silverman": 0.9 min(sd, IQR / 1.349) n^(-1/5), sd alone where IQR == 0; "scott": sd n^(-1 / (d + 4))."""
+    columns = np.asarray(columns, dtype=np.int64)
+    r = np.full((len(columns), 2), np.nan) if rng is None else np.array(rng, dtype=np.float64).reshape(len(columns), 2)
+    rule = bw if isinstance(bw, str) else None
+    if rule not in (None, "silverman", "scott"):
+        raise ValueError("%s: bw is \"silverman\", \"scott\", one number or one per entry" % what)
+    sd = q = None
+    if rule is not None or np.isnan(r).any():
+        sd, q = figures()
+        sd, q = np.asarray(sd)[columns], np.asarray(q)[columns]
+    if rule is None:
+        h = np.array(bw, dtype=np.float64).reshape(len(columns))
+    else:
+        with np.errstate(invalid="ignore"):
+            iqr = q[:, 2] - q[:, 1]
+            spread = np.where(iqr > 0.0, np.minimum(sd, iqr / 1.349), sd)
+        h = 0.9 * spread * float(n) ** -0.2 if rule == "silverman" else sd * float(n) ** (-1.0 / (d + 4))
+        for e in np.flatnonzero(~(np.isfinite(h) & (h > 0.0))):
+            raise ValueError("%s: the %s bandwidth of column %d comes out %r (a constant column, or one with NaN or infinite draws): give bw explicitly"
+                             % (what, rule, columns[e], float(h[e])))
+    auto = np.isnan(r)
+    if auto.any():
+        r = np.where(auto, np.stack([q[:, 0] - cut * h, q[:, 3] + cut * h], axis=1), r)
+        for e in np.flatnonzero(~np.isfinite(r).all(axis=1)):
+            raise ValueError("%s: the automatic bounds of column %d come out %r: give range explicitly" % (what, columns[e], tuple(r[e].tolist())))
+    return np.ascontiguousarray(h), np.ascontiguousarray(r)
+
+
+def _kde_bw_arg(bw, shape, what):
+    """a rule's name as it is; one number, or numbers of `shape` (for pairs (hx, hy) holds for all pairs) -> a float64 array of `shape`"""
+    if isinstance(bw, str):
+        return bw
+    try:
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(bw, dtype=np.float64), shape))
+    except ValueError:
+        raise ValueError("%s: bw is a rule's name, one number or an array of shape %s" % (what, shape)) from None
+
+
+def _kde_figures(summary):
+    """the figures the rules read, of one summary call over the window (it sorts all nvars columns)"""
+    def figures():
+        s = summary(probs=(0.0, 0.25, 0.75, 1.0), hdpi=None)
+        return s.sd, s.quantiles
+    return figures
+
+
+def _kde_result(call, summary, n, nvars, cols, points, bw, cut, rng, model=None):
+    """shared by Sampler.kde and kde_device: call(cols, ncols, npoints, range, bw, grid, density) -> rc"""
+    sel = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+    k, g = int(nvars) if sel is None else len(sel), min(max(int(points), 0), 4097)   # (beyond 2 .. 4096 stays beyond it: refused below)
+    columns = np.arange(k) if sel is None else sel
+    if sel is not None and ((sel < 0) | (sel >= nvars)).any():
+        h, r = np.ones(k), np.zeros((k, 2))                                 # a bad index is the call's to refuse
+    else:
+        h, r = _kde_rules(_kde_bw_arg(bw, (k,), "kde"), _range_arg(rng, (k, 2), "kde"), float(cut), n, 1, columns, _kde_figures(summary), "kde")
+    grid, dens = np.zeros((k, g)), np.zeros((k, g))
+    buf = sel if sel is None or k else np.zeros(1, dtype=np.int32)       # an empty list is a list (refused), not "all columns"
+    _capi.check(call(buf.ctypes.data_as(C.POINTER(C.c_int32)) if sel is not None else None, k if sel is not None else 0, g, _capi.dptr(r),
+                     _capi.dptr(h), _capi.dptr(grid), _capi.dptr(dens)), model)
+    return Kde(tuple(columns.tolist()), grid, dens, h)
+
+
+def _kde_pairs_result(call, summary, n, nvars, pairs, points, bw, cut, rng, model=None):
+    """shared by Sampler.kde_pairs and kde_pairs_device: call(pairs, npairs, npx, npy, range, bw, xgrid, ygrid, density) -> rc"""
+    pr = np.ascontiguousarray([[int(a), int(b)] for a, b in pairs], dtype=np.int32).reshape(-1, 2)
+    p = len(pr)
+    npx, npy = (int(points), int(points)) if np.ndim(points) == 0 else (int(points[0]), int(points[1]))
+    npx, npy = min(max(npx, 0), 257), min(max(npy, 0), 257)
+    if ((pr < 0) | (pr >= nvars)).any():
+        h, r = np.ones(2 * p), np.zeros((2 * p, 2))                         # a bad index is the call's to refuse
+    else:
+        rr = _range_arg(rng, (p, 2, 2), "kde_pairs")
+        bb = _kde_bw_arg(bw, (p, 2), "kde_pairs")
+        h, r = _kde_rules(bb if isinstance(bb, str) else bb.reshape(-1), None if rr is None else rr.reshape(-1, 2), float(cut), n, 2, pr.reshape(-1),
+                          _kde_figures(summary), "kde_pairs")
+    xg, yg, dens = np.zeros((p, npx)), np.zeros((p, npy)), np.zeros((p, npx, npy))
+    buf = pr if p else np.zeros((1, 2), dtype=np.int32)
+    _capi.check(call(buf.ctypes.data_as(C.POINTER(C.c_int32)), p, npx, npy, _capi.dptr(r), _capi.dptr(h), _capi.dptr(xg), _capi.dptr(yg),
+                     _capi.dptr(dens)), model)
+    return KdePairs(tuple((int(a), int(b)) for a, b in pr), xg, yg, dens, h.reshape(p, 2))
+
+
 class RankDiagnostics(NamedTuple):
     """Rank-normalised split R-hat, bulk and tail ESS (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021) per selected column.
     rhat = max(rhat_bulk, rhat_folded) (NaN where either is); truncated: bit 0 bulk, bit 1 lower tail, bit 2 upper tail -- where a bit
@@ -1154,6 +1261,36 @@ def histogram2d_device(ptr: int, chains: int, iterations: int, nvars: int, pairs
     return _histogram2d_result(call, pairs, bins, range)
 
 
+def kde_device(ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0, count: Optional[int] = None,
+               thin: int = 1, cols: Optional[Sequence[int]] = None, points: int = 512, bw="silverman", cut: float = 3.0, range=None) -> Kde:
+    """Gaussian kernel density estimates of the pooled kept iterations first + j * thin of a device buffer [chains][iterations][nvars]
+    (a sampler's draws, a predictor's to_host = False result, Comm.allgather_draws(to_host=False)), evaluated where the draws are
+    (rh_kde_device).  cols: the parameters asked for, in the result's order (None: all); points: 2 .. 4096 per curve.  bw:
+    "silverman" (0.9 min(sd, IQR / 1.349) N^(-1/5)), "scott" (sd N^(-1/5)), one number, or one per column.  range: None (every column
+    from min - cut * bw to max + cut * bw), one (lo, hi) for all columns, or one per column (None or (nan, nan): automatic).  A rule
+    or an automatic bound reads one summary_device call over the same window, which sorts all nvars columns; a column for which it
+    comes out zero or not finite (a constant one, one with NaN) raises ValueError: give bw and range."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    at = (C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count, int(thin))
+    call = lambda *a: _capi.lib().rh_kde_device(*at, *a)
+    summary = lambda **kw: summary_device(ptr, chains, iterations, nvars, device, first, count, thin, **kw)
+    return _kde_result(call, summary, int(chains) * _kept(count, thin), int(nvars), cols, points, bw, cut, range)
+
+
+def kde_pairs_device(ptr: int, chains: int, iterations: int, nvars: int, pairs: Sequence[Tuple[int, int]], device: int = 0, first: int = 0,
+                     count: Optional[int] = None, thin: int = 1, points=(64, 64), bw="scott", cut: float = 3.0, range=None) -> KdePairs:
+    """Joint Gaussian kernel density estimates of pairs of parameters over the pooled kept iterations of a device buffer
+    [chains][iterations][nvars] (rh_kde_pairs_device): a product kernel, evaluated as a matrix product on the fp64 matrix cores.
+    points: (npx, npy) or one number, 2 .. 256 each.  bw: "scott" (sd N^(-1/6) per axis), "silverman", one number, (hx, hy) for all
+    pairs, or [P][2].  range: None (automatic per axis, as kde_device's), one ((xlo, xhi), (ylo, yhi)) for all pairs, or one per pair.
+    A rule or an automatic bound reads one summary_device call over the same window, which sorts all nvars columns."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    at = (C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count, int(thin))
+    call = lambda *a: _capi.lib().rh_kde_pairs_device(*at, *a)
+    summary = lambda **kw: summary_device(ptr, chains, iterations, nvars, device, first, count, thin, **kw)
+    return _kde_pairs_result(call, summary, int(chains) * _kept(count, thin), int(nvars), pairs, points, bw, cut, range)
+
+
 def format_precis(names: Sequence[str], summary: Summary) -> str:
     """precis' table (rainier-notebook package.scala:393-417, without the correlations) as a string: Mean, StdDev and the first two
     order statistics of `summary`, %10.2f, one line per parameter."""
@@ -1283,6 +1420,33 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_histogram2d(self._h, int(first), count, int(thin), *a)
         return _histogram2d_result(call, pairs, bins, range, self.model._h)
+
+    def kde(self, first: int = 0, count: Optional[int] = None, thin: int = 1, cols: Optional[Sequence[int]] = None, points: int = 512,
+            bw="silverman", cut: float = 3.0, range=None) -> Kde:
+        """The smooth density of the parameters: Gaussian kernel density estimates over the kept iterations first + j * thin of all
+        chains pooled, evaluated where the draws are (rh_sampler_kde); only the curves come back.  cols: the parameters asked for, in
+        the result's order (None: all); points: 2 .. 4096 per curve.  bw: "silverman" (0.9 min(sd, IQR / 1.349) N^(-1/5)), "scott"
+        (sd N^(-1/5)), one number, or one per column.  range: None (every column from min - cut * bw to max + cut * bw), one (lo, hi)
+        for all columns, or one per column (None or (nan, nan): automatic); count = None: everything completed so far.  A rule or an
+        automatic bound reads one summary() call over the same window, which sorts all nVars columns; a column for which it comes
+        out zero or not finite (a constant one, one with NaN) raises ValueError: give bw and range.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_kde(self._h, int(first), count, int(thin), *a)
+        summary = lambda **kw: self.summary(first, count, thin, **kw)
+        return _kde_result(call, summary, self.chains * _kept(count, thin), self.model.nVars, cols, points, bw, cut, range, self.model._h)
+
+    def kde_pairs(self, pairs: Sequence[Tuple[int, int]], first: int = 0, count: Optional[int] = None, thin: int = 1, points=(64, 64),
+                  bw="scott", cut: float = 3.0, range=None) -> KdePairs:
+        """The smooth joint density of pairs of parameters over the same window (rh_sampler_kde_pairs): what the reference's contour
+        draws.  A product Gaussian kernel, evaluated as a matrix product on the fp64 matrix cores: 128 N exponentials per 64 x 64 tile
+        of the surface, not 4096 N.  points: (npx, npy) or one number, 2 .. 256 each.  bw: "scott" (sd N^(-1/6) per axis), "silverman", one number,
+        (hx, hy) for all pairs, or [P][2].  range: None (automatic per axis, as kde's), one ((xlo, xhi), (ylo, yhi)) for all pairs, or
+        one per pair.  A rule or an automatic bound reads one summary() call over the same window, which sorts all nVars columns.
+        The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_kde_pairs(self._h, int(first), count, int(thin), *a)
+        summary = lambda **kw: self.summary(first, count, thin, **kw)
+        return _kde_pairs_result(call, summary, self.chains * _kept(count, thin), self.model.nVars, pairs, points, bw, cut, range, self.model._h)
 
     def rank_diagnostics(self, first: int = 0, count: Optional[int] = None, cols: Optional[Sequence[int]] = None) -> RankDiagnostics:
         """Can this run be trusted: rank-normalised split R-hat, bulk ESS and tail ESS (Vehtari et al. 2021) of the parameters over
