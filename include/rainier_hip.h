@@ -49,7 +49,8 @@ extern "C" {
                                  rh_loo_quantile_device, rh_sampler_loo_quantile, rh_loo_quantile_lower_only,
                                  rh_sampler_joint_diagnostics, rh_joint_diagnostics_device, rh_joint_lower_only,
                                  rh_sampler_rank_plot, rh_rank_plot_device, rh_rank_plot_lower_only,
-                                 rh_sampler_kde, rh_kde_device, rh_sampler_kde_pairs, rh_kde_pairs_device, rh_kde_lower_only) */
+                                 rh_sampler_kde, rh_kde_device, rh_sampler_kde_pairs, rh_kde_pairs_device, rh_kde_lower_only,
+                                 rh_cross_covariance_device, rh_sampler_cross_covariance, rh_cross_covariance_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -499,6 +500,47 @@ int rh_covariance_device(const void *dev_draws, int32_t device, int32_t chains, 
 /* No device needed: the covariance kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_covariance_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- cross-covariance of two device-resident draw sets ----------------------------------------------------------------------------
+ * How parameter a moves with quantity b, where b was computed from the same draws (an observation's log-likelihood, a fitted value,
+ * a replicated observation): A^T B of the centred rows on the fp64 matrix cores (csrc/device/rh_xcov.hip.h), in a tile made for a
+ * narrow A (32 columns) and a wide B (128 columns); only Ka x Kb figures come back.  With B the pointwise log-likelihood,
+ * cross[k][i] = cov_post(theta_k, log p(y_i | theta)) is the first-order influence of observation i on the posterior mean of
+ * theta_k, the raw material of the infinitesimal-jackknife covariance (Giordano and Broderick, "The Bayesian infinitesimal jackknife
+ * for variance").
+ * Two buffers a [chains][iterations][na] and b [chains][iterations][nb] on one device; they may be one buffer.  Window, thinning and
+ * flat rows are rh_covariance_device's, the same for both: kept = ceil(count/thin), N = chains * kept >= 2, flat row r = c * kept + j
+ * is row first + j*thin of chain c in either buffer.  cols_a [Ka], cols_b [Kb]: duplicates allowed; NULL: all columns in order (the
+ * count then 0 or the buffer's columns).  A split is 4096 consecutive flat rows, S = ceil(N/4096):
+ *   mean_a[k], mean_b[k]  exactly rh_covariance_device's mean of that column: the same order, the same bits;
+ *   d[r][k]     = x[r][k] - mean[k], one rounding;
+ *   var_a[k], var_b[k]    per split one accumulator from +0.0 over r ascending, acc = fma(d, d, acc); the splits added in ascending s
+ *               from +0.0; the total divided by (double)(N - 1);
+ *   P_s[a][b]   = one accumulator from +0.0, r ascending in split s: acc = fma(dA[r][a], dB[r][b], acc);
+ *   cross[a][b] = (sum over s ascending of P_s[a][b]) / (double)(N - 1);
+ *   corr[a][b]  = cross[a][b] / (sqrt(var_a[a]) * sqrt(var_b[b])), IEEE operations in that order, not clamped; NaN where either
+ *                 variance is not finite and > 0.
+ * A NaN in a column makes that column's row (of a) or column (of b) of cross and corr NaN, together with its mean and variance, and
+ * touches nothing else.  Nothing depends on tiling, chunking, the order of either column list or the launch.  With b the buffer a,
+ * entry (a, b) of cross has the bits of entry (cols_a[a], cols_b[b]) of rh_covariance_device's cov over all columns.
+ * mean_a, var_a [Ka], mean_b, var_b [Kb], cross, corr [Ka][Kb]: caller-allocated on the host; each may be NULL, not all of them; corr
+ * needs no other output asked for.
+ * The partial sums live in a bounded device workspace (128 MiB, walked in chunks of tile pairs); a shape whose single tile pair is
+ * beyond it (S * 32 KiB, S > 4096) returns RH_E_UNSUPPORTED before any launch.  A broken window, N < 2, an index outside a buffer's
+ * columns, a count < 1 with a list, all outputs NULL: RH_E_INVALID, the message names the argument.  No device: RH_E_DEVICE (no CPU
+ * fallback).  Synchronises the device before and after. */
+int rh_cross_covariance_device(const void *dev_a, int32_t na, const void *dev_b, int32_t nb, int32_t device, int32_t chains, int32_t iterations,
+                               int32_t first, int32_t count, int32_t thin, const int32_t *cols_a, int32_t ncols_a, const int32_t *cols_b,
+                               int32_t ncols_b, double *mean_a, double *mean_b, double *var_a, double *var_b, double *cross, double *corr);
+/* a: the sampler's draws over the window; b: predictor p's requirements over the same window, [chains][kept][nreq], made on the
+ * device behind it and never copied out.  Goes to the sampler's stream behind its pending work, is not part of rh_timing and does
+ * not alter the chains; count <= iterations completed - first. */
+int rh_sampler_cross_covariance(rh_sampler *s, rh_predict *p, int32_t first, int32_t count, int32_t thin, const int32_t *cols_a, int32_t ncols_a,
+                                const int32_t *cols_b, int32_t ncols_b, double *mean_a, double *mean_b, double *var_a, double *var_b, double *cross,
+                                double *corr);
+/* No device needed: the cross-covariance kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_cross_covariance_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 /* ---- posterior histograms and joint count grids over device-resident draws ----------------------------------------------------
  * The shape of a posterior: the reference's density(seq, bounds) -- a histogram of one parameter's pooled draws between doubles.min

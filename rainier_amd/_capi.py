@@ -38,6 +38,8 @@ EXPORTS = [
     "rh_generate_create", "rh_generate_destroy", "rh_generate_nout", "rh_generate_device", "rh_sampler_generate", "rh_generate_lower_only", "rh_generate_ext_lower_only",
     # covariance / correlation over device-resident draws (rainier-notebook package.scala:79-98, MassMatrixEstimator.scala:38-47)
     "rh_sampler_covariance", "rh_covariance_device", "rh_covariance_lower_only",
+    # cross-covariance of two device-resident draw sets: parameters against quantities computed from the draws
+    "rh_cross_covariance_device", "rh_sampler_cross_covariance", "rh_cross_covariance_lower_only",
     # histograms / joint count grids over device-resident draws (rainier-notebook package.scala:63-98)
     "rh_sampler_histogram", "rh_histogram_device", "rh_histogram_lower_only",
     # Gaussian kernel density estimates over device-resident draws: curves and surfaces
@@ -179,6 +181,9 @@ def lib():
     L.rh_sampler_covariance.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, dp, dp, dp]
     L.rh_covariance_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, dp, dp, dp]
     L.rh_covariance_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_cross_covariance_device.argtypes = [vp, C.c_int32, vp, C.c_int32] + [C.c_int32] * 6 + [ip, C.c_int32, ip, C.c_int32] + [dp] * 6
+    L.rh_sampler_cross_covariance.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, ip, C.c_int32] + [dp] * 6
+    L.rh_cross_covariance_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     lp, i32 = C.POINTER(C.c_int64), C.c_int32
     L.rh_sampler_histogram.argtypes = [vp, i32, i32, i32, ip, i32, i32, dp, dp, lp, lp, lp, lp]
     L.rh_histogram_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ip, i32, i32, dp, dp, lp, lp, lp, lp]
@@ -401,6 +406,19 @@ def covariance_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_covariance_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def cross_covariance_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_xcov.hip.h behind rh_cov.hip.h (cross-covariance of two draw sets on the device: A^T B of the centred rows on
+    the fp64 matrix cores) -> code object for `arch`, without a device: compiled through the kernel cache and judged as before a
+    launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_cross_covariance_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how long the batches and how many splits of the joint diagnostics' three Grams, how many column tiles and edges of a histogram, how many grid tiles, surface tiles and chunks of a kernel density estimate, how many columns and lags of the rank diagnostics, how many segments of a chain and which splitter stride of the rank plots, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many tile pairs of a cross-covariance, how long the batches and how many splits of the joint diagnostics' three Grams, how many column tiles and edges of a histogram, how many grid tiles, surface tiles and chunks of a kernel density estimate, how many columns and lags of the rank diagnostics, how many segments of a chain and which splitter stride of the rank plots, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -28,6 +28,7 @@
 #include "device/rh_summary.hip.h"
 #include "device/rh_cov.hip.h"
 #include "device/rh_joint.hip.h"
+#include "device/rh_xcov.hip.h"
 #include "device/rh_hist.hip.h"
 #include "device/rh_kde.hip.h"
 #include "device/rh_rank.hip.h"
@@ -96,6 +97,28 @@ inline Covariance covariance_plan(long long chains, long long count, long long t
   P.per_pair = RC_PAIR_BYTES(P.S);
   P.over_cap = P.per_pair > cap;
   P.pc = std::max<long long>(1, std::min<long long>(cap / P.per_pair, P.pairs));
+  return P;
+}
+// ---- cross-covariance of two draw sets (device/rh_xcov.hip.h) ----
+struct CrossCovariance {
+  long long kept, N, S;          // kept iterations per chain; flat rows; splits of RC_SPLIT rows
+  long long ta, tb, pairs;       // A tiles of RX_TA columns, B tiles of RX_TB; tile pairs, p = ta * TB + tb
+  long long per_pair, pc;        // workspace bytes of one tile pair (its S partial tiles); tile pairs per chunk
+  bool over_cap;                 // one tile pair alone is beyond the cap
+};
+// Ka, Kb: the selected columns of either side; cap: RC_WS_CAP_BYTES (a parameter for the CPU tests' driver).  S 32 KiB saturates at
+// the largest long long (2^31 chains of 2^31 draws are beyond 64 bits of bytes)
+inline CrossCovariance cross_covariance_plan(long long chains, long long count, long long thin, long long Ka, long long Kb, long long cap = RC_WS_CAP_BYTES) {
+  CrossCovariance P = {};
+  P.kept = (count + thin - 1) / thin;
+  P.N = chains * P.kept;
+  P.S = (P.N + RC_SPLIT - 1) / RC_SPLIT;
+  P.ta = (Ka + RX_TA - 1) / RX_TA;
+  P.tb = (Kb + RX_TB - 1) / RX_TB;
+  P.pairs = P.ta * P.tb;
+  P.per_pair = P.S > 0x7fffffffffffffffll / RX_PAIR_BYTES(1) ? 0x7fffffffffffffffll : RX_PAIR_BYTES(P.S);
+  P.over_cap = P.per_pair > cap;
+  P.pc = std::max<long long>(1, std::min<long long>(cap / std::max<long long>(P.per_pair, 1), P.pairs));
   return P;
 }
 // ---- joint diagnostics: multivariate ESS and MPSRF (device/rh_joint.hip.h) ----

@@ -528,6 +528,66 @@ def covariance_device(ptr: int, chains: int, iterations: int, nvars: int, device
     return _covariance_result(call, nvars, cols, corr)
 
 
+class CrossCovariance(NamedTuple):
+    """How the columns of one draw set move with those of another computed from the same draws: mean_a, var_a [Ka], mean_b, var_b
+    [Kb] (pooled sample figures of the kept draws, divisor N - 1), cross [Ka][Kb] (entry (a, b): the covariance of column cols_a[a]
+    of the first with column cols_b[b] of the second), corr [Ka][Kb] (None when not asked for; NaN where a column has no variance)."""
+    mean_a: np.ndarray
+    mean_b: np.ndarray
+    var_a: np.ndarray
+    var_b: np.ndarray
+    cross: np.ndarray
+    corr: Optional[np.ndarray]
+    cols_a: Tuple[int, ...]
+    cols_b: Tuple[int, ...]
+
+
+class Influence(NamedTuple):
+    """Local case sensitivity of the posterior means and their infinitesimal-jackknife covariance (Giordano and Broderick, "The
+    Bayesian infinitesimal jackknife for variance"): influence [K][n], entry (k, i) = cov_post(theta_k, log p(y_i | theta)), the
+    first-order effect of up-weighting observation i on the posterior mean of parameter cols[k]; ij_cov [K][K] =
+    sum_i (I_i - Ibar)(I_i - Ibar)^T with I_i column i of influence and Ibar the mean of the columns, an estimate of the frequentist
+    sampling covariance of the posterior means that stays valid when the model is misspecified; ij_se [K] = sqrt(diag(ij_cov));
+    post_sd [K], the posterior standard deviations to hold them against."""
+    influence: np.ndarray
+    ij_cov: np.ndarray
+    ij_se: np.ndarray
+    post_sd: np.ndarray
+    cols: Tuple[int, ...]
+    ll_cols: Tuple[int, ...]
+
+
+def _cross_covariance_result(call, na, nb, cols_a, cols_b, corr, model=None):
+    """shared by Sampler.cross_covariance and cross_covariance_device: call(cols_a, ncols_a, cols_b, ncols_b, mean_a, mean_b, var_a,
+    var_b, cross, corr) -> rc"""
+    lists = []
+    for cols, n in ((cols_a, na), (cols_b, nb)):
+        sel = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+        k = int(n) if sel is None else len(sel)
+        buf = sel if sel is None or k else np.zeros(1, dtype=np.int32)   # an empty list is a list (refused), not "all columns"
+        lists.append((sel, k, buf))
+    (sa, ka, ba), (sb, kb, bb) = lists
+    ip = C.POINTER(C.c_int32)
+    mean_a, mean_b, var_a, var_b, cross, cr = np.zeros(ka), np.zeros(kb), np.zeros(ka), np.zeros(kb), np.zeros((ka, kb)), np.zeros((ka, kb)) if corr else None
+    _capi.check(call(ba.ctypes.data_as(ip) if sa is not None else None, ka if sa is not None else 0, bb.ctypes.data_as(ip) if sb is not None else None,
+                     kb if sb is not None else 0, _capi.dptr(mean_a), _capi.dptr(mean_b), _capi.dptr(var_a), _capi.dptr(var_b), _capi.dptr(cross),
+                     _capi.dptr(cr) if corr else None), model)
+    return CrossCovariance(mean_a, mean_b, var_a, var_b, cross, cr, tuple(range(ka)) if sa is None else tuple(sa.tolist()),
+                           tuple(range(kb)) if sb is None else tuple(sb.tolist()))
+
+
+def cross_covariance_device(a_ptr: int, b_ptr: int, chains: int, iterations: int, na: int, nb: int, device: int = 0, first: int = 0,
+                            count: Optional[int] = None, thin: int = 1, cols_a: Optional[Sequence[int]] = None,
+                            cols_b: Optional[Sequence[int]] = None, corr: bool = False) -> CrossCovariance:
+    """The pooled cross-covariance (and, with corr = True, the cross-correlation) of the columns of two device buffers
+    [chains][iterations][na] and [chains][iterations][nb] over the kept iterations first + j * thin, computed where they are
+    (rh_cross_covariance_device): a sampler's draws against a predictor's to_host = False result, say.  The two may be one buffer."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_cross_covariance_device(C.c_void_p(a_ptr), int(na), C.c_void_p(b_ptr), int(nb), int(device), int(chains),
+                                                             int(iterations), int(first), count, int(thin), *a)
+    return _cross_covariance_result(call, na, nb, cols_a, cols_b, corr)
+
+
 class Histogram(NamedTuple):
     """The shape of single parameters (the reference's density(seq, bounds), rainier-notebook package.scala:63-77): for column k
     (parameter cols[k]) edges [K][nbins + 1], counts [K][nbins] (int64; bin b holds edges[b] <= x < edges[b + 1], the last bin is
@@ -1400,6 +1460,29 @@ class Sampler:
         count = self.progress()[1] - int(first) if count is None else int(count)
         call = lambda *a: _capi.lib().rh_sampler_covariance(self._h, int(first), count, int(thin), *a)
         return _covariance_result(call, self.model.nVars, cols, corr, self.model._h)
+
+    def cross_covariance(self, predictor: Predictor, first: int = 0, count: Optional[int] = None, thin: int = 1,
+                         cols: Optional[Sequence[int]] = None, pred_cols: Optional[Sequence[int]] = None, corr: bool = False) -> CrossCovariance:
+        """How the parameters move with the predictor's requirements (fitted values, log-likelihoods, ...) over the kept iterations
+        first + j * thin of all chains: the chains x kept x requirements matrix is made on the device behind the draws and the
+        cross-covariance (with corr = True the cross-correlation too) computed there (rh_sampler_cross_covariance); only
+        parameters x requirements figures come back.  cols, pred_cols: the parameters and the requirements asked for (None: all);
+        count = None: everything completed so far.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_cross_covariance(self._h, predictor._h, int(first), count, int(thin), *a)
+        return _cross_covariance_result(call, self.model.nVars, predictor.nreq, cols, pred_cols, corr, self.model._h)
+
+    def influence(self, ll_predictor: Predictor, first: int = 0, count: Optional[int] = None, thin: int = 1,
+                  cols: Optional[Sequence[int]] = None, ll_cols: Optional[Sequence[int]] = None) -> Influence:
+        """Which observations drive a coefficient, and how far the posterior means would move under resampling of the data
+        (Giordano and Broderick, "The Bayesian infinitesimal jackknife for variance").  ll_predictor's requirements are the
+        log-likelihoods log p(y_i | theta) of the n observations.  influence[k][i] = cov_post(theta_k, log p(y_i | theta)) is one
+        cross_covariance call; from its K x n figures, in numpy: ij_cov = sum_i (I_i - Ibar)(I_i - Ibar)^T, I_i column i of
+        influence and Ibar the mean of the columns; ij_se = sqrt(diag(ij_cov)); post_sd = sqrt(var of the parameters)."""
+        r = self.cross_covariance(ll_predictor, first, count, thin, cols, ll_cols)
+        d = r.cross - r.cross.mean(axis=1, keepdims=True)
+        ij_cov = d @ d.T
+        return Influence(r.cross, ij_cov, np.sqrt(np.diag(ij_cov)), np.sqrt(r.var_a), r.cols_a, r.cols_b)
 
     def histogram(self, first: int = 0, count: Optional[int] = None, thin: int = 1, cols: Optional[Sequence[int]] = None, bins: int = 20,
                   range=None) -> Histogram:
