@@ -50,7 +50,8 @@ extern "C" {
                                  rh_sampler_joint_diagnostics, rh_joint_diagnostics_device, rh_joint_lower_only,
                                  rh_sampler_rank_plot, rh_rank_plot_device, rh_rank_plot_lower_only,
                                  rh_sampler_kde, rh_kde_device, rh_sampler_kde_pairs, rh_kde_pairs_device, rh_kde_lower_only,
-                                 rh_cross_covariance_device, rh_sampler_cross_covariance, rh_cross_covariance_lower_only) */
+                                 rh_cross_covariance_device, rh_sampler_cross_covariance, rh_cross_covariance_lower_only,
+                                 rh_linear_create, rh_linear_destroy, rh_linear_nout, rh_linear_device, rh_sampler_linear, rh_linear_lower_only) */
 
 enum rh_status {
   RH_OK = 0,
@@ -541,6 +542,42 @@ int rh_sampler_cross_covariance(rh_sampler *s, rh_predict *p, int32_t first, int
 /* No device needed: the cross-covariance kernels' code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
  * launch; *code_out is malloc'ed, freed with rh_free. */
 int rh_cross_covariance_lower_only(const char *arch, void **code_out, size_t *code_size);
+
+/* ---- a linear map of device-resident draws -----------------------------------------------------------------------------------------
+ * Y = (X[:, cols] - c) W + b with the rows kept, on the fp64 matrix cores (csrc/device/rh_linear.hip.h): new columns from the draws
+ * without a compiled program.  W = L^-T of the covariance's Cholesky factor and c the mean give whitened draws, and their squared
+ * norms the Mahalanobis distances; W the eigenvectors, principal-component scores; W of +-1, contrasts; W the transposed design
+ * matrix and b the intercept column, the linear predictor of a GLM at M new rows.  The result is a draw set [chains][kept][M] on the
+ * device that every other *_device call here takes.
+ * A map is W [K][M] row-major (1 <= K, M <= 4096: at most 128 MiB on the device), center [K] or NULL, offset [M] or NULL, cols [K]
+ * (the columns of the draws the K rows of W meet, duplicates allowed, none negative) or NULL for 0 .. K-1; all copied.  device -1:
+ * bound to the device of the first call.  Window and flat rows are rh_covariance_device's: kept = ceil(count/thin), N = chains * kept,
+ * flat row r = c * kept + j is row first + j*thin of chain c.
+ *   d[r][k]   = x[r][cols[k]] - center[k], one rounding (center NULL: x itself);
+ *   y[r][m]   = one accumulator from +0.0 over k ascending, acc = fma(d[r][k], W[k][m], acc); with offset, y = acc + offset[m];
+ *   sqnorm[r] = one accumulator from +0.0 over m ascending, acc = fma(y[r][m], y[r][m], acc).
+ * A NaN in a selected value of row r makes row r of y and sqnorm[r] NaN and touches no other row.  Nothing depends on tiling, the
+ * grid, the launch or a repeat; no atomics, no workspace.
+ * host_y [chains][kept][M] and host_sqnorm [chains][kept]: caller-allocated on the host; *dev_y and *dev_sqnorm: the handle's own
+ * device buffers of those shapes, valid until the handle's next call.  Each of the four may be NULL, not all of them; with neither y
+ * asked for, Y is never written to memory.  A NULL argument, K or M outside 1 .. 4096, a negative column (create); a NULL handle or
+ * buffer, a broken window, a column >= nvars, all outputs NULL, another device than the handle's: RH_E_INVALID, the message names the
+ * argument.  No device: RH_E_DEVICE (no CPU fallback), after those checks.  rh_linear_device runs on the null stream and
+ * synchronises before and after. */
+typedef struct rh_linear rh_linear;
+int rh_linear_create(const double *W, int32_t K, int32_t M, const double *center, const double *offset, const int32_t *cols, int32_t device,
+                     rh_linear **out);
+void rh_linear_destroy(rh_linear *h);
+int rh_linear_nout(const rh_linear *h);   /* M; -1 for NULL */
+int rh_linear_device(rh_linear *h, const void *dev_draws, int32_t device, int32_t chains, int32_t iterations, int32_t nvars, int32_t first,
+                     int32_t count, int32_t thin, double *host_y, void **dev_y, double *host_sqnorm, void **dev_sqnorm);
+/* over the sampler's draws: goes to its stream behind its pending work, is not part of rh_timing and does not alter the chains;
+ * count <= iterations completed - first. */
+int rh_sampler_linear(rh_sampler *s, rh_linear *h, int32_t first, int32_t count, int32_t thin, double *host_y, void **dev_y, double *host_sqnorm,
+                      void **dev_sqnorm);
+/* No device needed: the linear map kernel's code object for `arch` (NULL: gfx950) through the kernel cache, judged as before a
+ * launch; *code_out is malloc'ed, freed with rh_free. */
+int rh_linear_lower_only(const char *arch, void **code_out, size_t *code_size);
 
 /* ---- posterior histograms and joint count grids over device-resident draws ----------------------------------------------------
  * The shape of a posterior: the reference's density(seq, bounds) -- a histogram of one parameter's pooled draws between doubles.min

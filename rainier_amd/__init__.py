@@ -7,7 +7,7 @@
 """
 from .sampler import (Check, Covariance, CrossCovariance, DefaultConfig, DenseMassMatrixTuner, DensityFunction, DiagonalMassMatrix,  # noqa: F401
                       DiagonalMassMatrixTuner,
-                      DualAvgTuner, EHMC, EHMCSampler, Generator, HMC, Histogram, Histogram2d, HMCSampler, IdentityMassMatrixTuner, Influence, JointDiagnostics, Kde, KdePairs, Loo, LooExpect, LooQuantile, Mcse, Model, NUTSSampler, Ppc, Predictor, RankDiagnostics, RankPlot,
+                      DualAvgTuner, EHMC, EHMCSampler, Generator, HMC, Histogram, Histogram2d, HMCSampler, IdentityMassMatrixTuner, Influence, JointDiagnostics, Kde, KdePairs, LinearMap, Loo, LooExpect, LooQuantile, Mahalanobis, Mcse, Model, NUTSSampler, Ppc, Predictor, RankDiagnostics, RankPlot,
                       RainierHipError, Sampler, SamplerConfig, StaticMassMatrix, StaticStepSize, Summary, Trace, covariance_device, cross_covariance_device,
-                      diagnostics, diagnostics_device, format_precis, gen, generate_device, histogram2d_device, histogram_device, joint_diagnostics_device, kde_device, kde_pairs_device, loo_compare, loo_device, loo_expect_device, loo_quantile_device, make_config, mcse_device, ppc, ppc_device, predict, predict_device, rank_diagnostics_device, rank_plot_device, sample_multi,
+                      diagnostics, diagnostics_device, format_precis, gen, generate_device, histogram2d_device, histogram_device, joint_diagnostics_device, kde_device, kde_pairs_device, linear_device, loo_compare, loo_device, loo_expect_device, loo_quantile_device, make_config, mcse_device, ppc, ppc_device, predict, predict_device, rank_diagnostics_device, rank_plot_device, sample_multi,
                       summary_device)

@@ -40,6 +40,8 @@ EXPORTS = [
     "rh_sampler_covariance", "rh_covariance_device", "rh_covariance_lower_only",
     # cross-covariance of two device-resident draw sets: parameters against quantities computed from the draws
     "rh_cross_covariance_device", "rh_sampler_cross_covariance", "rh_cross_covariance_lower_only",
+    # a linear map of device-resident draws, the rows kept: whitening, Mahalanobis distances, scores, contrasts, GLM predictors
+    "rh_linear_create", "rh_linear_destroy", "rh_linear_nout", "rh_linear_device", "rh_sampler_linear", "rh_linear_lower_only",
     # histograms / joint count grids over device-resident draws (rainier-notebook package.scala:63-98)
     "rh_sampler_histogram", "rh_histogram_device", "rh_histogram_lower_only",
     # Gaussian kernel density estimates over device-resident draws: curves and surfaces
@@ -184,6 +186,13 @@ def lib():
     L.rh_cross_covariance_device.argtypes = [vp, C.c_int32, vp, C.c_int32] + [C.c_int32] * 6 + [ip, C.c_int32, ip, C.c_int32] + [dp] * 6
     L.rh_sampler_cross_covariance.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, ip, C.c_int32] + [dp] * 6
     L.rh_cross_covariance_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rh_linear_create.argtypes = [dp, C.c_int32, C.c_int32, dp, dp, ip, C.c_int32, C.POINTER(vp)]
+    L.rh_linear_destroy.argtypes = [vp]
+    L.rh_linear_destroy.restype = None
+    L.rh_linear_nout.argtypes = [vp]
+    L.rh_linear_device.argtypes = [vp, vp] + [C.c_int32] * 7 + [dp, C.POINTER(vp), dp, C.POINTER(vp)]
+    L.rh_sampler_linear.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(vp), dp, C.POINTER(vp)]
+    L.rh_linear_lower_only.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
     lp, i32 = C.POINTER(C.c_int64), C.c_int32
     L.rh_sampler_histogram.argtypes = [vp, i32, i32, i32, ip, i32, i32, dp, dp, lp, lp, lp, lp]
     L.rh_histogram_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ip, i32, i32, dp, dp, lp, lp, lp, lp]
@@ -419,6 +428,19 @@ def cross_covariance_lower_only(arch: str = "gfx950") -> bytes:
     L = lib()
     code, n = C.c_void_p(), C.c_size_t(0)
     check(L.rh_cross_covariance_lower_only(arch.encode(), C.byref(code), C.byref(n)))
+    try:
+        return C.string_at(code, n.value)
+    finally:
+        L.rh_free(code)
+
+
+def linear_lower_only(arch: str = "gfx950") -> bytes:
+    """csrc/device/rh_linear.hip.h behind rh_cov.hip.h (a linear map of the draws on the device: (X - c) W + b on the fp64 matrix
+    cores, the rows kept) -> code object for `arch`, without a device: compiled through the kernel cache and judged as before a
+    launch (no spills, no scratch, isacheck)."""
+    L = lib()
+    code, n = C.c_void_p(), C.c_size_t(0)
+    check(L.rh_linear_lower_only(arch.encode(), C.byref(code), C.byref(n)))
     try:
         return C.string_at(code, n.value)
     finally:

@@ -1,5 +1,5 @@
 // draws_plan.hpp -- the launch plans of the calls over device-resident draws (draws.cpp): how many parameters share a bounded
-// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many tile pairs of a cross-covariance, how long the batches and how many splits of the joint diagnostics' three Grams, how many column tiles and edges of a histogram, how many grid tiles, surface tiles and chunks of a kernel density estimate, how many columns and lags of the rank diagnostics, how many segments of a chain and which splitter stride of the rank plots, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
+// workspace, how many tiles and merge passes, which order statistics, how many tile pairs of a covariance, how many tile pairs of a cross-covariance, how many row tiles and m tiles of a linear map, how long the batches and how many splits of the joint diagnostics' three Grams, how many column tiles and edges of a histogram, how many grid tiles, surface tiles and chunks of a kernel density estimate, how many columns and lags of the rank diagnostics, how many segments of a chain and which splitter stride of the rank plots, how many series of the standard errors and which order statistics bracket a quantile, how long the tail of a PSIS column, how many pairs of a leave-one-out expectation or of its quantiles and scores, how many rows and lanes of a predictive check, which predict kernel, how many sampling tiles and slabs.  Arithmetic only: no HIP, no allocation,
 // no globals.  draws.cpp launches what these functions say, and the CPU tests' drivers of the device text walk the same plan.
 #ifndef RH_DRAWS_PLAN_HPP
 #define RH_DRAWS_PLAN_HPP
@@ -29,6 +29,7 @@
 #include "device/rh_cov.hip.h"
 #include "device/rh_joint.hip.h"
 #include "device/rh_xcov.hip.h"
+#include "device/rh_linear.hip.h"
 #include "device/rh_hist.hip.h"
 #include "device/rh_kde.hip.h"
 #include "device/rh_rank.hip.h"
@@ -282,6 +283,30 @@ inline void kde_grid(double lo, double hi, int G, double *g) {
   g[0] = lo;
   for (int i = 1; i < G - 1; i++) g[i] = lo + ((double)i * (hi - lo)) / (double)(G - 1);
   g[G - 1] = hi;
+}
+// ---- a linear map of the draws (device/rh_linear.hip.h) ----
+struct Linear {
+  long long kept, N;             // kept iterations per chain; flat rows
+  long long rt, mt, slabs;       // row tiles of RL_TR flat rows; m tiles of RL_TM output columns; slabs of RC_SLAB k per m tile
+  long long mgroups, mper;       // workgroups per row tile; m tiles of each
+  long long grid;                // rt * mgroups
+  long long y_bytes, sq_bytes;   // of y [N][M] and sqnorm [N]; 0 where not asked for (saturated like the density plans' bytes)
+};
+// K, M: the map's shape.  sqnorm carries a row's chain across the m tiles in one workgroup; without it, and with fewer than
+// RL_FULL_GRID row tiles, every m tile gets a workgroup of its own
+inline Linear linear_plan(long long chains, long long count, long long thin, long long K, long long M, bool want_y, bool want_sqnorm) {
+  Linear P = {};
+  P.kept = (count + thin - 1) / thin;
+  P.N = chains * P.kept;
+  P.rt = (P.N + RL_TR - 1) / RL_TR;
+  P.mt = (M + RL_TM - 1) / RL_TM;
+  P.slabs = (K + RC_SLAB - 1) / RC_SLAB;
+  P.mgroups = want_sqnorm || P.rt >= RL_FULL_GRID ? 1 : P.mt;
+  P.mper = P.mt / P.mgroups;
+  P.grid = kde_sat_mul(P.rt, P.mgroups);
+  P.y_bytes = want_y ? kde_sat_mul(kde_sat_mul(P.N, M), 8) : 0;
+  P.sq_bytes = want_sqnorm ? kde_sat_mul(P.N, 8) : 0;
+  return P;
 }
 // ---- rank-normalised split R-hat, bulk and tail ESS (device/rh_rank.hip.h) ----
 struct Rank {

@@ -588,6 +588,73 @@ def cross_covariance_device(a_ptr: int, b_ptr: int, chains: int, iterations: int
     return _cross_covariance_result(call, na, nb, cols_a, cols_b, corr)
 
 
+class LinearMap:
+    """rh_linear: Y = (X[:, cols] - center) W + offset over draws that stay on the device (Sampler.linear, linear_device), on the fp64
+    matrix cores.  W [K][M]; center [K], offset [M] (None: none); cols: the K columns of the draws that the rows of W meet, duplicates
+    allowed (None: 0 .. K-1).  nout = M.  The result [chains][kept][M] is a draw set that summary_device, histogram_device, kde_device,
+    cross_covariance_device and diagnostics_device take as it lies."""
+
+    def __init__(self, W, center=None, offset=None, cols: Optional[Sequence[int]] = None, device: int = -1):
+        self._h = C.c_void_p()
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2:
+            raise ValueError("LinearMap: W must be a K x M matrix")
+        k, m = W.shape
+        vec = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        center, offset = vec(center), vec(offset)
+        cc = None if cols is None else np.ascontiguousarray([int(c) for c in cols], dtype=np.int32)
+        for v, n, what in ((center, k, "center"), (offset, m, "offset"), (cc, k, "cols")):
+            if v is not None and len(v) != n:
+                raise ValueError("LinearMap: %s has %d entries, W is %d x %d" % (what, len(v), k, m))
+        _capi.check(_capi.lib().rh_linear_create(_capi.dptr(W), k, m, None if center is None else _capi.dptr(center),
+                                                 None if offset is None else _capi.dptr(offset),
+                                                 None if cc is None else cc.ctypes.data_as(C.POINTER(C.c_int32)), int(device), C.byref(self._h)))
+        self.nin, self.nout = k, _capi.lib().rh_linear_nout(self._h)
+
+    def close(self):
+        if self._h:
+            _capi.lib().rh_linear_destroy(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+
+
+def _linear_result(call, lmap, chains, kept, to_host, sqnorm, model=None):
+    """shared by Sampler.linear and linear_device: call(host_y, byref(dev_y), host_sqnorm, byref(dev_sqnorm)) -> rc.  sqnorm: False (y),
+    True (y, sqnorm) or "only" (sqnorm: y is then not asked for and never written to memory)"""
+    y = sqnorm != "only"
+    out_y = np.zeros((chains, kept, lmap.nout)) if y and to_host else None
+    out_sq = np.zeros((chains, kept)) if sqnorm and to_host else None
+    py, psq = C.c_void_p(), C.c_void_p()
+    _capi.check(call(None if out_y is None else _capi.dptr(out_y), C.byref(py) if y and not to_host else None,
+                     None if out_sq is None else _capi.dptr(out_sq), C.byref(psq) if sqnorm and not to_host else None), model)
+    r = (out_y, out_sq) if to_host else (py.value, psq.value)
+    return r[1] if not y else r if sqnorm else r[0]
+
+
+def linear_device(lmap: LinearMap, ptr: int, chains: int, iterations: int, nvars: int, device: int = 0, first: int = 0,
+                  count: Optional[int] = None, thin: int = 1, to_host: bool = True, sqnorm=False):
+    """(X[:, cols] - center) W + offset over the kept iterations first + j * thin of a device buffer [chains][iterations][nvars],
+    computed where it is (rh_linear_device).  Returns y [chains][kept][M], or with sqnorm = True (y, sqnorm [chains][kept]), the squared
+    norm of every row of y, or with sqnorm = "only" sqnorm alone (y is then never written to memory); to_host = False: the device
+    pointers of the map's own buffers, valid until its next call."""
+    count = int(iterations) - int(first) if count is None else int(count)
+    call = lambda *a: _capi.lib().rh_linear_device(lmap._h, C.c_void_p(ptr), int(device), int(chains), int(iterations), int(nvars), int(first), count,
+                                                   int(thin), *a)
+    return _linear_result(call, lmap, int(chains), _kept(count, thin), to_host, sqnorm)
+
+
+class Mahalanobis(NamedTuple):
+    """d2 [chains][kept]: the squared Mahalanobis distance (x - mean)^T cov^-1 (x - mean) of every kept draw from the pooled mean under
+    the pooled covariance of the same window (a device pointer with to_host = False); mean [K], cov [K][K]: what it was measured
+    with; cols: the parameters.  For a Gaussian posterior d2 is chi-squared with K degrees of freedom."""
+    d2: object
+    mean: np.ndarray
+    cov: np.ndarray
+    cols: Tuple[int, ...]
+
+
 class Histogram(NamedTuple):
     """The shape of single parameters (the reference's density(seq, bounds), rainier-notebook package.scala:63-77): for column k
     (parameter cols[k]) edges [K][nbins + 1], counts [K][nbins] (int64; bin b holds edges[b] <= x < edges[b + 1], the last bin is
@@ -1373,6 +1440,7 @@ class Sampler:
         one (internal 48-bit state, pending nextNextGaussian or None) per chain (what Driver.sample does with the caller's rng)."""
         self.model = model
         self._nn = None
+        self._d2_map = None          # mahalanobis(to_host = False): the map whose buffer holds the last d2
         if rng_states is not None:
             seeds = [int(st) ^ 0x5DEECE66D for st, _ in rng_states]
             self._nn = np.array([np.nan if g is None else float(g) for _, g in rng_states], dtype=np.float64)
@@ -1483,6 +1551,40 @@ class Sampler:
         d = r.cross - r.cross.mean(axis=1, keepdims=True)
         ij_cov = d @ d.T
         return Influence(r.cross, ij_cov, np.sqrt(np.diag(ij_cov)), np.sqrt(r.var_a), r.cols_a, r.cols_b)
+
+    def linear(self, lmap: LinearMap, first: int = 0, count: Optional[int] = None, thin: int = 1, to_host: bool = True, sqnorm=False):
+        """(X[:, cols] - center) W + offset of the draws where they are (rh_sampler_linear) over the kept iterations first + j * thin:
+        y [chains][kept][M], or with sqnorm = True (y, sqnorm [chains][kept]), the squared norm of every row of y, or with
+        sqnorm = "only" sqnorm alone (y is then never written to memory); to_host = False: the device pointers of the map's own
+        buffers, which summary_device, kde_device, ... take.  count = None: everything completed so far.  The chains are not altered."""
+        count = self.progress()[1] - int(first) if count is None else int(count)
+        call = lambda *a: _capi.lib().rh_sampler_linear(self._h, lmap._h, int(first), count, int(thin), *a)
+        return _linear_result(call, lmap, self.chains, _kept(count, thin), to_host, sqnorm, self.model._h)
+
+    def mahalanobis(self, first: int = 0, count: Optional[int] = None, thin: int = 1, cols: Optional[Sequence[int]] = None,
+                    to_host: bool = True) -> Mahalanobis:
+        """The squared Mahalanobis distance of every kept draw from the pooled mean under the pooled covariance of the window: which
+        chain sits outside the bulk jointly, how close the posterior is to a Gaussian (d2 ~ chi-squared with K degrees of freedom),
+        and, up to a constant, the Gaussian proposal's log-density of importance and bridge schemes.  The recipe: r = covariance(first,
+        count, thin, cols); cov = L L^T by numpy's Cholesky; W = solve(L, I).T; LinearMap(W, center = r.mean, cols = r.cols); d2 is
+        the sqnorm of one linear call that asks for nothing else, so the whitened draws are never written to memory.  The whitened
+        draws themselves are linear(..., to_host = False) with the same map.  With to_host = False d2 is the device pointer of a
+        buffer that lives until this sampler's next mahalanobis call.  A covariance that is not positive definite: ValueError."""
+        r = self.covariance(first, count, thin, cols)
+        try:
+            if not np.all(np.isfinite(r.cov)):
+                raise np.linalg.LinAlgError
+            L = np.linalg.cholesky(r.cov)
+        except np.linalg.LinAlgError:
+            raise ValueError("mahalanobis: the covariance of the columns %s is not positive definite" % (list(r.cols),)) from None
+        lmap = LinearMap(np.linalg.solve(L, np.eye(len(L))).T, center=r.mean, cols=r.cols)
+        d2 = self.linear(lmap, first, count, thin, to_host, sqnorm="only")
+        if self._d2_map is not None:
+            self._d2_map.close()
+        self._d2_map = None if to_host else lmap     # to_host = False: d2 lies in the map's own buffer
+        if to_host:
+            lmap.close()
+        return Mahalanobis(d2, r.mean, r.cov, r.cols)
 
     def histogram(self, first: int = 0, count: Optional[int] = None, thin: int = 1, cols: Optional[Sequence[int]] = None, bins: int = 20,
                   range=None) -> Histogram:
